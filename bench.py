@@ -18,7 +18,10 @@
              (2 x 38 GB of 288 GB) with the collectives over gloo -- the same launch, model build, barriers, score
              exchange and rank-0 line as the 8-GPU run, at ~0.5x per-rank throughput (NOT a scaling number).
 
-Prints ONE JSON line on rank 0 (see the driver contract) with two extra objects:
+A plain run sets up, warms up, times the --steps latents and prints ONE JSON line on rank 0 (see the driver contract);
+`--dump-outputs DIR` then also writes what the timed path returned in its last step (DIR/latents.npy, float32) and the round's
+verifier scores (DIR/scores.npy, DIR/labels.npy), after the timed region.  Everything else the bench measures or checks runs only
+with `--full`: the timed latent's parity against the per-step path, power / clock telemetry, and the extra objects
     roofline     -- the dominant kernel class (the 256x256-tile bf16 MFMA GEMM; persistent whole-tile launches of the ping-pong loop): algorithmic FLOPs of its launches /
                     their summed durations, both taken INSIDE the real forward sequence: right after the timed
                     region one more candidate is denoised for a few steps with the library's in-sequence timing hook
@@ -28,6 +31,8 @@ Prints ONE JSON line on rank 0 (see the driver contract) with two extra objects:
     cpu_baseline -- the CPU oracle (a port of the reference path) on the host's physical cores over a bounded sample:
                     cfg1 (256^2, 4 steps, fp32) end to end, and one warmed DoubleStream + SingleStream block at
                     the cfg2 sequence length extrapolated to the metric's unit (labelled as extrapolated).
+    attention, vae, text_encoders, training -- the attention kernels' isolated cost, the VAE and text-encoder timings and one
+                    LoRA training step (each reported separately from the metric).
 """
 from __future__ import annotations
 
@@ -890,6 +895,16 @@ def launch_check(args):
         torch.distributed.destroy_process_group()
 
 
+def dump_outputs(path, latent, scores):
+    """What the timed path handed its caller in the last timed step: the latent generate() returned (bf16 -> float32, exact) and
+    the round boundary's verifier records.  ~1 MB at 1024^2."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "latents.npy"), latent.float().cpu().numpy())
+    np.save(os.path.join(path, "scores.npy"), np.array([s for s, _ in scores], dtype=np.float32))
+    np.save(os.path.join(path, "labels.npy"), np.array([lab for _, lab in scores], dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -897,6 +912,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--res", type=int, default=1024)
     ap.add_argument("--denoise-steps", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity check, telemetry and the separately reported tables (roofline, attention, VAE, text "
+                         "encoders, CPU baseline, training); the --no-* options below switch single parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed latent and the round's scores as DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-isolated-shapes", action="store_true")
@@ -985,7 +1005,7 @@ def main():
         if shard.world_size > 1:
             torch.distributed.barrier()
 
-    tele = Telemetry(local) if shard.rank == 0 else None
+    tele = Telemetry(local) if shard.rank == 0 and args.full else None
     coll_dev = dev if backend == "nccl" else torch.device("cpu")
 
     def round_boundary(lat_list, seed_list, n_round):
@@ -1008,7 +1028,7 @@ def main():
         torch.cuda.empty_cache()
     torch.cuda.synchronize()
     barrier()
-    smi0 = amdsmi_snapshot(local) if shard.rank == 0 else None
+    smi0 = amdsmi_snapshot(local) if shard.rank == 0 and args.full else None
     t0 = time.perf_counter()
     outs = []
     for i in range(args.steps):
@@ -1023,7 +1043,7 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     t_end = t0 + dt
-    smi1 = amdsmi_snapshot(local) if shard.rank == 0 else None
+    smi1 = amdsmi_snapshot(local) if shard.rank == 0 and args.full else None
     per_rank = None
     if shard.world_size > 1:
         # MAX over ranks: a device tensor over RCCL, a host tensor over gloo (gloo has no GPU all_reduce here)
@@ -1038,12 +1058,14 @@ def main():
                     "round_boundary_ms": [round(float(v) * 1e3, 2) for v in every[:, 1]],
                     "peak_hbm_gib": [round(float(v), 1) for v in every[:, 2]]}
     assert all(torch.isfinite(o.float()).all() for o in outs), "non-finite latents"
+    if args.dump_outputs and shard.rank == 0 and outs:
+        dump_outputs(args.dump_outputs, outs[-1], scores)
 
     # the timed region proves RESULTS, not only work: the first timed latent -- produced by the fast path
     # (one C call / one hipGraph replay for the T steps) -- against the same candidate on the general PER-STEP path
     # (tranformer_forward + scheduler.step per step, eager launches), which the GPU parity suite pins to the oracle
     parity = None
-    if not args.no_parity_check and shard.rank == 0 and not args.lean:
+    if args.full and not args.no_parity_check and shard.rank == 0 and not args.lean:
         import hashlib
         noop = lambda pipe_, i_, t_, kw: {}                  # noqa: E731 -- a callback selects the general path
         sd0 = seeds[args.warmup]
@@ -1123,7 +1145,7 @@ def main():
             res["INVALID"] = "rehearsal: all ranks on one GPU (plumbing check, not a scaling measurement)"
         if args.small:
             res["INVALID"] = "debug model (--small), not the BASELINE workload"
-        if shard.world_size == 1:
+        if shard.world_size == 1 and args.full:
             if not args.no_roofline:
                 res["roofline"] = in_sequence_roofline(lambda steps: one_latent(seeds[0], steps), PROFILE_STEPS,
                                                        dt / args.steps * 1e3 / T, (S_txt, S_img, D, mlp))

@@ -41,7 +41,7 @@ import sys
 sys.path.insert(0, %(root)r)
 from reflectionflow_amd import _lib
 _lib.LIB_PATH = %(so)r
-sys.argv = ["bench.py", "--no-cpu-baseline", "--no-train", "--no-vae", "--no-text", "--no-attention-table", "--no-isolated-shapes",
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-train", "--no-vae", "--no-text", "--no-attention-table", "--no-isolated-shapes",
             "--steps", "%(steps)d", "--warmup", "1"]
 import bench
 bench.main()

@@ -4,8 +4,9 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/final
 mkdir -p $OUT
-python bench.py --steps 3 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
-( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/prof -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-isolated-shapes > $GRAFT_REPO_ROOT/$OUT/bench_prof.json 2> $GRAFT_REPO_ROOT/$OUT/bench_prof.err )
+ROOT=$PWD
+python bench.py --full --steps 3 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
+( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof -o bench -- python $ROOT/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-isolated-shapes > $ROOT/$OUT/bench_prof.json 2> $ROOT/$OUT/bench_prof.err )
 bash tools/pmc_collect.sh > $OUT/pmc_collect.log 2>&1
 python tools/pmc_parse.py r02 > $OUT/pmc_parse.log 2>&1
 python tools/bench_cfg4.py > $OUT/cfg4.json 2> $OUT/cfg4.err

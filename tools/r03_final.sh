@@ -4,8 +4,9 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/final4
 mkdir -p $OUT
-python bench.py --steps 3 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
-( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/prof -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-isolated-shapes --no-graph > $GRAFT_REPO_ROOT/$OUT/bench_prof.json 2> $GRAFT_REPO_ROOT/$OUT/bench_prof.err )
+ROOT=$PWD
+python bench.py --full --steps 3 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
+( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof -o bench -- python $ROOT/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-isolated-shapes --no-graph > $ROOT/$OUT/bench_prof.json 2> $ROOT/$OUT/bench_prof.err )
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/prof_vae_sites -o sites -- python $GRAFT_REPO_ROOT/tools/trace_vae_callsites.py > $GRAFT_REPO_ROOT/$OUT/vae_sites.log 2>&1 )
 bash tools/pmc_collect.sh > $OUT/pmc_collect.log 2>&1
 python tools/pmc_parse.py r03 > $OUT/pmc_parse.log 2>&1

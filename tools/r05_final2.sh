@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout 1500 python -m pytest tests -q -m gpu -x > $OUT/gpu_suite.log 2>&1; tail -3 $OUT/gpu_suite.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log
-timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err </dev/null; tail -c 400 $OUT/bench_default.json
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err </dev/null; tail -c 400 $OUT/bench_default.json
 timeout 600 python bench.py --train-only --steps 2 --warmup 1 --train-batch 8 > $OUT/bench_train_batch8.json 2> $OUT/bench_train_batch8.err </dev/null
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_train -o train -- python bench.py --train-only --steps 2 --warmup 1 > $OUT/bench_train_prof.json 2> $OUT/bench_train_prof.err </dev/null
 f=$(find $OUT/prof_train -name "*kernel_trace.csv" | head -1)
