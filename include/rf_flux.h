@@ -36,7 +36,8 @@ typedef enum rf_status {
 
 const char* rf_last_error(void);
 /* ABI version: bump on any struct/signature change (v13: rf_attn_bwd_desc.kernel, rf_lora_adamw / rf_lora_prodigy; v14: rf_lora_fuse /
- * rf_lora_unfuse_grads, rf_qkv_train_fwd's forward-only form; v15: rf_lora_clip_grad_norm). */
+ * rf_lora_unfuse_grads, rf_qkv_train_fwd's forward-only form; v15: rf_lora_clip_grad_norm; v16: the CLIP-score verifier,
+ * rf_clip_vision_weights / rf_clip_preprocess / rf_clip_vision_encode / rf_clip_score). */
 int rf_abi_version(void);
 /* Returns 950 when the library was compiled for gfx950. */
 int rf_target_arch(void);
@@ -484,6 +485,46 @@ int64_t rf_clip_text_workspace_bytes(const rf_clip_weights* w, int32_t B, int32_
  * sequence b (eos_pos: HOST array [B]) */
 int rf_clip_text_encode(const rf_clip_weights* w, const int32_t* ids, int32_t B, int32_t S, const int32_t* eos_pos, void* last_hidden, void* pooled,
                         const rf_workspace* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * CLIP-score verifier: transformers' CLIPModel (clip-vit-large-patch14 layout) on what the reference's verifier
+ * reads, the candidate's 8-bit PNG (tts/tts_reflectionflow.py:157-170, 345-352), scored against the original prompt:
+ *   score[b] = exp(logit_scale) * cos(visual_projection(post_layernorm(ViT(pixels_b))[0]), text_projection(CLIPTextModel(prompt).pooled))
+ * The image side stays on the device: rf_clip_preprocess (8-bit levels, CLIPImageProcessor's resize / crop / normalise, im2col)
+ * -> rf_clip_vision_encode (patch GEMM, class + position embeddings, pre_layrnorm, the text tower's encoder layers, post_layernorm
+ * of row 0, visual_projection) -> rf_clip_score.  Every projection of the vision tower runs on ONE pinned GEMM schedule
+ * (whole 256x256 tiles, no split-K / stream-K), so an image's embedding does not depend on how many images share the call.
+ * ---------------------------------------------------------------------------------- */
+typedef struct rf_clip_vision_weights {
+  int32_t layers, hidden, heads, inter;   /* hidden = 64 * heads <= 4096, inter % 64 == 0 */
+  int32_t image_size, patch, proj_dim;    /* tokens T = (image_size / patch)^2 + 1 <= 512; K_pad = round_up(3 patch^2, 64) */
+  int32_t mask_S;                         /* = round_up(T, 32): the mask's size */
+  float eps; int32_t _pad;                /* layer_norm_eps (1e-5) */
+  const void* patch_w;                    /* patch_embedding.weight as [hidden][K_pad], columns (c, ky, kx), zero beyond 3 patch^2 */
+  const void* class_embed;                /* [hidden] */
+  const void* pos_embed;                  /* position_embedding.weight [T][hidden] */
+  const void *pre_ln_scale, *pre_ln_shift;    /* pre_layrnorm as (weight - 1, bias) */
+  const void *post_ln_scale, *post_ln_shift;  /* post_layernorm as (weight - 1, bias) */
+  const void* proj;                       /* visual_projection.weight [proj_dim][hidden] (no bias) */
+  const float* mask;                      /* [mask_S][mask_S] fp32: 0 in columns < T, -inf in the padded columns */
+  const rf_clip_layer* layer;             /* HOST array [layers], as rf_clip_weights (1/8 folded into q, v bias into b_o) */
+} rf_clip_vision_weights;
+/* B images -> im2col patch rows [B * (size / patch)^2][K_pad] bf16 (rows in raster order of the patches, columns (c, ky, kx), zero
+ * beyond 3 patch^2).  Image b, row y, pixel x, channel c (0..2) is img[b * s_img + y * s_row + x * s_pix + c * s_ch] (bf16, element
+ * strides: the VAE's zero-halo NHWC output at its interior, or a [3][H][W] tensor of 8-bit levels).  Per pixel: level =
+ * rint(255 clamp(a v + b, 0, 1)) (the PNG's 8-bit value; a = b = 0.5 for a decoded image in [-1, 1], a = 1 / 255, b = 0 for levels);
+ * then CLIPImageProcessor: resize the shortest edge to `size` (long edge int(size * long / short)) with antialiased bicubic
+ * (a = -0.5, PIL's filter; horizontal pass, rounded and clipped to 8 bits, then vertical pass, as PIL's 8-bit resample), round to
+ * 8-bit levels, centre-crop size x size (offset (new - size) / 2, floored), (v / 255 - mean) / std
+ * with CLIP's mean / std.  H, W <= 8192, size % patch == 0. */
+int rf_clip_preprocess(const void* img, int64_t s_img, int64_t s_row, int64_t s_pix, int64_t s_ch, int32_t B, int32_t H, int32_t W, float a,
+                       float b, int32_t size, int32_t patch, void* patches, void* stream);
+int64_t rf_clip_vision_workspace_bytes(const rf_clip_vision_weights* w, int32_t B);
+/* patches [B * (image_size / patch)^2][K_pad] (rf_clip_preprocess) -> image_embeds [B][proj_dim] bf16; 1 <= B <= 64 */
+int rf_clip_vision_encode(const rf_clip_vision_weights* w, const void* patches, int32_t B, void* image_embeds, const rf_workspace* ws, void* stream);
+/* scores[b] = exp(logit_scale) * <img_b / |img_b|, txt / |txt|> in fp32 (img [B][P], txt [P] bf16; logit_scale = the model's
+ * log-domain parameter); one workgroup per row, fixed reduction order */
+int rf_clip_score(const void* img, const void* txt, float logit_scale, float* scores, int32_t B, int32_t P, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * TRAINING path: backward of the same blocks, for the LoRA reflection tuning of

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librf_flux.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 RF_EPI_STORE, RF_EPI_GELU, RF_EPI_GATE_RES, RF_EPI_QKV, RF_EPI_QKV_GELU = range(5)
 # rf_gemm_schedule (rf_gemm_desc.schedule): how ONE launch is cut into workgroups; AUTO everywhere in the product
@@ -163,6 +163,13 @@ class rf_clip_weights(C.Structure):
                 ("final_ln_scale", C.c_void_p), ("final_ln_shift", C.c_void_p), ("layer", C.POINTER(rf_clip_layer))]
 
 
+class rf_clip_vision_weights(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("layers", "hidden", "heads", "inter", "image_size", "patch", "proj_dim", "mask_S")] + \
+               [("eps", C.c_float), ("_pad", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("patch_w", "class_embed", "pos_embed", "pre_ln_scale", "pre_ln_shift", "post_ln_scale", "post_ln_shift",
+                                          "proj", "mask")] + [("layer", C.POINTER(rf_clip_layer))]
+
+
 # every symbol include/rf_flux.h (the product ABI) declares: (restype, argtypes)
 _SIGS = {
     "rf_last_error": (C.c_char_p, []),
@@ -201,6 +208,12 @@ _SIGS = {
     "rf_t5_encode": (C.c_int, [C.POINTER(rf_t5_weights), _P, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(rf_workspace), _P]),
     "rf_clip_text_workspace_bytes": (C.c_int64, [C.POINTER(rf_clip_weights), C.c_int32, C.c_int32]),
     "rf_clip_text_encode": (C.c_int, [C.POINTER(rf_clip_weights), _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _P, _P, C.POINTER(rf_workspace), _P]),
+    # CLIP-score verifier (csrc/clip_vision.hip)
+    "rf_clip_preprocess": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                     C.c_int32, C.c_int32, _P, _P]),
+    "rf_clip_vision_workspace_bytes": (C.c_int64, [C.POINTER(rf_clip_vision_weights), C.c_int32]),
+    "rf_clip_vision_encode": (C.c_int, [C.POINTER(rf_clip_vision_weights), _P, C.c_int32, _P, C.POINTER(rf_workspace), _P]),
+    "rf_clip_score": (C.c_int, [_P, _P, C.c_float, _P, C.c_int32, C.c_int32, _P]),
     # training path
     "rf_qkv_train_fwd": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float,
                                    _P, _P, _P, _P, _P, _P, _P]),

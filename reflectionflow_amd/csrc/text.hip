@@ -13,14 +13,9 @@
 //     [heads or 1][S_pad][S_pad] (T5: bucketed relative positions; CLIP: the causal mask; both: -inf on padded keys);
 //   * row kernels (HBM-bound, 16-byte accesses): embedding gather (+ position rows), T5 RMS norm, gelu_new(a) * b, quick_gelu.
 #include "common.hpp"
+#include "text_internal.hpp"
 
 namespace rf {
-
-#define RF_TRY(expr)              \
-  do {                            \
-    int _rc = (expr);             \
-    if (_rc != RF_OK) return _rc; \
-  } while (0)
 
 static inline int grid_for(int64_t n, int per_block = 256) { return (int)((n + per_block - 1) / per_block); }
 
@@ -114,7 +109,6 @@ __global__ __launch_bounds__(256) void fill_bf16_rows_kernel(bf16_t* __restrict_
 }
 
 // ---- attention, head dim 64, <= 512 keys ----------------------------------------------------------------------------------------
-constexpr int TA_MAXS = 512;
 constexpr int TA_NT = TA_MAXS / 16;   // score tiles of 16 keys
 static inline int ta_lds_bytes(int S_pad) { return S_pad * 128 + 64 * (S_pad * 2 + 16); }
 
@@ -236,35 +230,13 @@ __global__ __launch_bounds__(256) void attn64_kernel(const bf16_t* __restrict__ 
   }   // it
 }
 
-// ---- host side ------------------------------------------------------------------------------------------------------------------
-struct TextCtx {
-  hipStream_t st;
-  bf16_t *X, *Xn, *QK, *VT, *AO, *HID, *G, *ones;
-  void* sk; int64_t sk_bytes;
-  int S, S_pad, B;
-};
-
-struct TextSizes { int64_t x, qk, vt, ao, hid, g, total; };
-constexpr int64_t TEXT_SK = 4096 + (64ll << 20);
-
-static TextSizes text_sizes(int rows, int D, int inner, int F, int hid_cols) {   // rows = B * S_pad
-  TextSizes z;
-  z.x = round_up((int64_t)rows * D * 2, 256);
-  z.qk = round_up((int64_t)rows * 2 * inner * 2, 256);
-  z.vt = round_up((int64_t)inner * rows * 2, 256);
-  z.ao = round_up((int64_t)rows * inner * 2, 256);
-  z.hid = round_up((int64_t)rows * hid_cols * 2, 256);
-  z.g = round_up((int64_t)rows * F * 2, 256);
-  z.total = 2 * z.x + z.qk + z.vt + z.ao + z.hid + z.g + round_up(16384 * 2, 256) + TEXT_SK;
-  return z;
-}
-
-static int text_ctx(TextCtx& c, const TextSizes& z, int B, int S, int S_pad, const rf_workspace* ws, hipStream_t st, const char* who) {
+// ---- host side (TextCtx / TextSizes: text_internal.hpp) ------------------------------------------------------------------------
+int text_ctx(TextCtx& c, const TextSizes& z, int B, int S, int S_pad, const rf_workspace* ws, hipStream_t st, const char* who) {
   RF_REQUIRE(ws && ws->base && aligned16(ws->base) && ws->bytes >= z.total, RF_ERR_WORKSPACE, "%s: workspace %lld < required %lld bytes", who,
              (long long)(ws ? ws->bytes : 0), (long long)z.total);
   char* p = (char*)ws->base;
   auto take = [&](int64_t bytes) { char* q = p; p += round_up(bytes, 256); return q; };
-  c.st = st; c.S = S; c.S_pad = S_pad; c.B = B;
+  c.st = st; c.S = S; c.S_pad = S_pad; c.B = B; c.sched = RF_SCHED_AUTO;
   c.X = (bf16_t*)take(z.x); c.Xn = (bf16_t*)take(z.x); c.QK = (bf16_t*)take(z.qk); c.VT = (bf16_t*)take(z.vt);
   c.AO = (bf16_t*)take(z.ao); c.HID = (bf16_t*)take(z.hid); c.G = (bf16_t*)take(z.g);
   c.ones = (bf16_t*)take(16384 * 2);
@@ -278,8 +250,8 @@ static int text_ctx(TextCtx& c, const TextSizes& z, int B, int S, int S_pad, con
 }
 
 // y[M x N] = epi(x[M x K] . w[N x K]^T + b) (+ residual)
-static int text_gemm(TextCtx& c, const bf16_t* x, int64_t ldx, const void* w, const void* b, int M, int N, int K, bf16_t* y, int64_t ldy, int epi,
-                     const bf16_t* residual) {
+int text_gemm(TextCtx& c, const bf16_t* x, int64_t ldx, const void* w, const void* b, int M, int N, int K, bf16_t* y, int64_t ldy, int epi,
+              const bf16_t* residual) {
   rf_gemm_desc d;
   memset(&d, 0, sizeof(d));
   d.N = N; d.num_groups = 1; d.epilogue = residual ? RF_EPI_GATE_RES : epi;
@@ -288,6 +260,10 @@ static int text_gemm(TextCtx& c, const bf16_t* x, int64_t ldx, const void* w, co
   G.seg[0].A = x; G.seg[0].lda = ldx; G.seg[0].W = w; G.seg[0].ldw = K; G.seg[0].K = K;
   G.bias = b; G.M = M; G.out = y; G.ldo = ldy;
   if (residual) { G.gate = c.ones; G.residual = residual; G.ldr = ldy; }
+  if (c.sched != RF_SCHED_AUTO) {   // a caller-pinned schedule (the CLIP vision tower: batch-invariant rows), no split-K scratch
+    d.schedule = c.sched; d.splitk_ws = nullptr; d.splitk_ws_bytes = 0;
+    return rf_gemm_bf16(&d, c.st);
+  }
   // A 512-token prompt is 2 rows of 256-tiles: 32 .. 160 output tiles with 64 .. 160 K-tiles each neither fill the 256 CUs with whole
   // tiles nor suit the 128-tile kernel AUTO picks below 200 tiles (417 TF): stream-K cuts the K-tile iterations evenly over the CUs
   {
@@ -297,7 +273,7 @@ static int text_gemm(TextCtx& c, const bf16_t* x, int64_t ldx, const void* w, co
   return rf_gemm_bf16(&d, c.st);
 }
 
-static int text_attention(TextCtx& c, int heads, int inner, const float* bias, int64_t bias_hs, float scale) {
+int text_attention(TextCtx& c, int heads, int inner, const float* bias, int64_t bias_hs, float scale) {
   const int lds = ta_lds_bytes(c.S_pad);
   static bool attr = false;
   if (!attr) {
@@ -316,6 +292,32 @@ static int text_attention(TextCtx& c, int heads, int inner, const float* bias, i
     hipLaunchKernelGGL(attn64_kernel<1>, dim3(cdiv(c.S_pad, 64), heads, c.B), dim3(256), lds, c.st, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner,
                        c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO, (int64_t)inner, c.S, c.S_pad, scale);
   RF_LAUNCH_CHECK();
+  return RF_OK;
+}
+
+// The pre-LN CLIP encoder layers over the residual stream c.X (B sequences of S_pad rows, width D, MLP width F): shared by the text
+// tower (causal mask) and the vision tower (padded keys masked).  Every GEMM goes through text_gemm, i.e. c.sched decides the schedule.
+int clip_layers(TextCtx& c, const rf_clip_layer* layer, int layers, int heads, int D, int F, const float* mask, float eps, const char* who) {
+  const int R = c.B * c.S_pad;
+  hipStream_t st = c.st;
+  for (int i = 0; i < layers; ++i) {
+    const rf_clip_layer& L = layer[i];
+    RF_REQUIRE(L.ln1_scale && L.ln1_shift && L.w_qk && L.b_qk && L.w_v && L.w_o && L.b_o && L.ln2_scale && L.ln2_shift && L.w_fc1 && L.b_fc1 && L.w_fc2 &&
+                   L.b_fc2, RF_ERR_NULL, "%s: layer %d has NULL weights", who, i);
+    RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, D, R, D, L.ln1_scale, L.ln1_shift, eps, st));
+    RF_TRY(text_gemm(c, c.Xn, D, L.w_qk, L.b_qk, R, 2 * D, D, c.QK, 2 * D, RF_EPI_STORE, nullptr));
+    RF_TRY(text_gemm(c, (const bf16_t*)L.w_v, D, c.Xn, nullptr, D, R, D, c.VT, R, RF_EPI_STORE, nullptr));
+    RF_TRY(text_attention(c, heads, D, mask, 0, 1.0f));
+    RF_TRY(text_gemm(c, c.AO, D, L.w_o, L.b_o, R, D, D, c.X, D, RF_EPI_STORE, c.X));
+    RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, D, R, D, L.ln2_scale, L.ln2_shift, eps, st));
+    RF_TRY(text_gemm(c, c.Xn, D, L.w_fc1, L.b_fc1, R, F, D, c.HID, F, RF_EPI_STORE, nullptr));
+    {
+      ProfScope prof(RF_KC_ROWOP, (double)R * F * 4, st);
+      hipLaunchKernelGGL(quick_gelu_kernel, dim3(grid_for((int64_t)R * F / 8)), dim3(256), 0, st, c.HID, (int64_t)R * F / 8);
+      RF_LAUNCH_CHECK();
+    }
+    RF_TRY(text_gemm(c, c.HID, F, L.w_fc2, L.b_fc2, R, D, F, c.X, D, RF_EPI_STORE, c.X));
+  }
   return RF_OK;
 }
 
@@ -428,24 +430,7 @@ extern "C" int rf_clip_text_encode(const rf_clip_weights* w, const int32_t* ids,
                        ids, c.X, S, S_pad, R, D, w->vocab);
     RF_LAUNCH_CHECK();
   }
-  for (int i = 0; i < w->layers; ++i) {
-    const rf_clip_layer& L = w->layer[i];
-    RF_REQUIRE(L.ln1_scale && L.ln1_shift && L.w_qk && L.b_qk && L.w_v && L.w_o && L.b_o && L.ln2_scale && L.ln2_shift && L.w_fc1 && L.b_fc1 && L.w_fc2 &&
-                   L.b_fc2, RF_ERR_NULL, "rf_clip_text_encode: layer %d has NULL weights", i);
-    RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, D, R, D, L.ln1_scale, L.ln1_shift, w->eps, st));
-    RF_TRY(text_gemm(c, c.Xn, D, L.w_qk, L.b_qk, R, 2 * D, D, c.QK, 2 * D, RF_EPI_STORE, nullptr));
-    RF_TRY(text_gemm(c, (const bf16_t*)L.w_v, D, c.Xn, nullptr, D, R, D, c.VT, R, RF_EPI_STORE, nullptr));
-    RF_TRY(text_attention(c, w->heads, D, w->mask, 0, 1.0f));
-    RF_TRY(text_gemm(c, c.AO, D, L.w_o, L.b_o, R, D, D, c.X, D, RF_EPI_STORE, c.X));
-    RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, D, R, D, L.ln2_scale, L.ln2_shift, w->eps, st));
-    RF_TRY(text_gemm(c, c.Xn, D, L.w_fc1, L.b_fc1, R, F, D, c.HID, F, RF_EPI_STORE, nullptr));
-    {
-      ProfScope prof(RF_KC_ROWOP, (double)R * F * 4, st);
-      hipLaunchKernelGGL(quick_gelu_kernel, dim3(grid_for((int64_t)R * F / 8)), dim3(256), 0, st, c.HID, (int64_t)R * F / 8);
-      RF_LAUNCH_CHECK();
-    }
-    RF_TRY(text_gemm(c, c.HID, F, L.w_fc2, L.b_fc2, R, D, F, c.X, D, RF_EPI_STORE, c.X));
-  }
+  RF_TRY(clip_layers(c, w->layer, w->layers, w->heads, D, F, w->mask, w->eps, "rf_clip_text_encode"));
   RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, D, R, D, w->final_ln_scale, w->final_ln_shift, w->eps, st));
   for (int b = 0; b < B; ++b) {
     const bf16_t* src = c.Xn + (int64_t)b * S_pad * D;

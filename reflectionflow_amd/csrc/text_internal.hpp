@@ -1,0 +1,48 @@
+// Internal interface of text.hip shared with clip_vision.hip (not part of the C ABI): the encoder context over a caller-owned
+// workspace, the projection GEMM, the head-dim-64 attention and the pre-LN CLIP layer loop.  The text towers keep their shape-based
+// GEMM policy (TextCtx::sched = RF_SCHED_AUTO); the vision tower pins one schedule for every projection (clip_vision.hip).
+#pragma once
+#include "common.hpp"
+
+#ifndef RF_TRY
+#define RF_TRY(expr)              \
+  do {                            \
+    int _rc = (expr);             \
+    if (_rc != RF_OK) return _rc; \
+  } while (0)
+#endif
+
+namespace rf {
+
+constexpr int TA_MAXS = 512;   // keys of attn64_kernel
+
+struct TextCtx {
+  hipStream_t st;
+  bf16_t *X, *Xn, *QK, *VT, *AO, *HID, *G, *ones;
+  void* sk; int64_t sk_bytes;
+  int S, S_pad, B;
+  int sched;   // rf_gemm_schedule of every text_gemm launch: RF_SCHED_AUTO = the shape-based policy of text_gemm
+};
+
+struct TextSizes { int64_t x, qk, vt, ao, hid, g, total; };
+constexpr int64_t TEXT_SK = 4096 + (64ll << 20);
+
+inline TextSizes text_sizes(int rows, int D, int inner, int F, int hid_cols) {   // rows = B * S_pad
+  TextSizes z;
+  z.x = round_up((int64_t)rows * D * 2, 256);
+  z.qk = round_up((int64_t)rows * 2 * inner * 2, 256);
+  z.vt = round_up((int64_t)inner * rows * 2, 256);
+  z.ao = round_up((int64_t)rows * inner * 2, 256);
+  z.hid = round_up((int64_t)rows * hid_cols * 2, 256);
+  z.g = round_up((int64_t)rows * F * 2, 256);
+  z.total = 2 * z.x + z.qk + z.vt + z.ao + z.hid + z.g + round_up(16384 * 2, 256) + TEXT_SK;
+  return z;
+}
+
+int text_ctx(TextCtx& c, const TextSizes& z, int B, int S, int S_pad, const rf_workspace* ws, hipStream_t st, const char* who);
+int text_gemm(TextCtx& c, const bf16_t* x, int64_t ldx, const void* w, const void* b, int M, int N, int K, bf16_t* y, int64_t ldy, int epi,
+              const bf16_t* residual);
+int text_attention(TextCtx& c, int heads, int inner, const float* bias, int64_t bias_hs, float scale);
+int clip_layers(TextCtx& c, const rf_clip_layer* layer, int layers, int heads, int D, int F, const float* mask, float eps, const char* who);
+
+}  // namespace rf

@@ -4,6 +4,7 @@ What the reference runs for every candidate's prompt (train_flux/flux/generate.p
 per candidate and round in tts/tts_reflectionflow.py:286-294, where the prompt changes with every reflection):
     pooled_prompt_embeds = CLIPTextModel(clip_ids [B, 77]).pooler_output
     prompt_embeds        = T5EncoderModel(t5_ids [B, 512])[0]
+`HipClipVisionEncoder` (+ `clip_score`) is the image side of the CLIP-score verifier (tts/clip_verifier.py).
 `HipT5Encoder` / `HipClipTextEncoder` take a Hugging Face `transformers`-layout state dict (so text_encoder_2/*.safetensors and
 text_encoder/model.safetensors load unchanged, with or without the `text_model.` prefix) and token ids; `HipTextEncoders` is the
 `pipe.text_encoder` callable of flux/pipeline.py (prompt -> (prompt_embeds, pooled)) once a tokenizer callable is supplied --
@@ -158,19 +159,7 @@ class HipClipTextEncoder:
         self.device, self.heads, self.hidden, self.eos_token_id = device, num_heads, D, eos_token_id
         k = self._k = _Keep(device)
         f = lambda t: t.detach().float()  # noqa: E731
-        self._layers = (L.rf_clip_layer * n_layers)()
-        for i in range(n_layers):
-            p = f"encoder.layers.{i}."
-            y = self._layers[i]
-            y.ln1_scale, y.ln1_shift = k.t(f(sd[p + "layer_norm1.weight"]) - 1.0), k.t(sd[p + "layer_norm1.bias"])
-            y.ln2_scale, y.ln2_shift = k.t(f(sd[p + "layer_norm2.weight"]) - 1.0), k.t(sd[p + "layer_norm2.bias"])
-            y.w_qk = k.t(torch.cat([f(sd[p + "self_attn.q_proj.weight"]) * 0.125, f(sd[p + "self_attn.k_proj.weight"])], 0))
-            y.b_qk = k.t(torch.cat([f(sd[p + "self_attn.q_proj.bias"]) * 0.125, f(sd[p + "self_attn.k_proj.bias"])], 0))
-            y.w_v = k.t(sd[p + "self_attn.v_proj.weight"])
-            wo = f(sd[p + "self_attn.out_proj.weight"])
-            y.w_o, y.b_o = k.t(wo), k.t(f(sd[p + "self_attn.out_proj.bias"]) + wo @ f(sd[p + "self_attn.v_proj.bias"]))
-            y.w_fc1, y.b_fc1 = k.t(sd[p + "mlp.fc1.weight"]), k.t(sd[p + "mlp.fc1.bias"])
-            y.w_fc2, y.b_fc2 = k.t(sd[p + "mlp.fc2.weight"]), k.t(sd[p + "mlp.fc2.bias"])
+        self._layers = _clip_layers(k, sd, n_layers)
         w = self._w = L.rf_clip_weights()
         w.layers, w.hidden, w.heads, w.inter = n_layers, D, num_heads, sd["encoder.layers.0.mlp.fc1.weight"].shape[0]
         w.vocab, w.max_pos, w.eps = sd["embeddings.token_embedding.weight"].shape[0], sd["embeddings.position_embedding.weight"].shape[0], eps
@@ -221,6 +210,131 @@ class HipClipTextEncoder:
         pos = ids.argmax(-1) if self.eos_token_id == 2 else (ids == self.eos_token_id).int().argmax(-1)
         pooled = last[torch.arange(B, device=self.device), pos]
         return last, pooled
+
+
+def _clip_layers(k: "_Keep", sd: Dict[str, torch.Tensor], n_layers: int) -> "C.Array":
+    """rf_clip_layer records of a CLIP encoder (text or vision tower: the same pre-LN layer): q|k concatenated with 1/sqrt(64) folded
+    into q, LayerNorm weights as (w - 1, b), v_proj.bias folded into the out-projection bias (softmax rows sum to 1)."""
+    f = lambda t: t.detach().float()  # noqa: E731
+    layers = (L.rf_clip_layer * n_layers)()
+    for i in range(n_layers):
+        p = f"encoder.layers.{i}."
+        y = layers[i]
+        y.ln1_scale, y.ln1_shift = k.t(f(sd[p + "layer_norm1.weight"]) - 1.0), k.t(sd[p + "layer_norm1.bias"])
+        y.ln2_scale, y.ln2_shift = k.t(f(sd[p + "layer_norm2.weight"]) - 1.0), k.t(sd[p + "layer_norm2.bias"])
+        y.w_qk = k.t(torch.cat([f(sd[p + "self_attn.q_proj.weight"]) * 0.125, f(sd[p + "self_attn.k_proj.weight"])], 0))
+        y.b_qk = k.t(torch.cat([f(sd[p + "self_attn.q_proj.bias"]) * 0.125, f(sd[p + "self_attn.k_proj.bias"])], 0))
+        y.w_v = k.t(sd[p + "self_attn.v_proj.weight"])
+        wo = f(sd[p + "self_attn.out_proj.weight"])
+        y.w_o, y.b_o = k.t(wo), k.t(f(sd[p + "self_attn.out_proj.bias"]) + wo @ f(sd[p + "self_attn.v_proj.bias"]))
+        y.w_fc1, y.b_fc1 = k.t(sd[p + "mlp.fc1.weight"]), k.t(sd[p + "mlp.fc1.bias"])
+        y.w_fc2, y.b_fc2 = k.t(sd[p + "mlp.fc2.weight"]), k.t(sd[p + "mlp.fc2.bias"])
+    return layers
+
+
+class HipClipVisionEncoder:
+    """CLIPVisionModel + visual_projection of a Hugging Face `CLIPModel` state dict (`vision_model.*`, `visual_projection.weight`; the
+    prefix may be absent): images -> image_embeds [B, projection_dim] bf16 (rf_clip_preprocess + rf_clip_vision_encode).
+    Same weight repacking as HipClipTextEncoder; the conv patch embedding becomes a [hidden, K_pad] GEMM weight (columns (c, ky, kx),
+    zero-padded to a multiple of 64)."""
+
+    MAX_BATCH = 64
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], num_heads: int, device, eps: float = 1e-5):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RFError(f"HipClipVisionEncoder: device {device}; the HIP path has no CPU fallback")
+        L.load()
+        sd = {(k[len("vision_model."):] if k.startswith("vision_model.") else k): v for k, v in state_dict.items()}
+        if "visual_projection.weight" not in sd:
+            raise RFError("HipClipVisionEncoder: the state dict has no visual_projection.weight (a CLIPModel state dict is needed)")
+        n_layers = 0
+        while f"encoder.layers.{n_layers}.layer_norm1.weight" in sd:
+            n_layers += 1
+        if n_layers == 0:
+            raise RFError("HipClipVisionEncoder: no vision_model.encoder.layers.* keys in the state dict")
+        pw = sd["embeddings.patch_embedding.weight"]                     # [hidden, 3, p, p]
+        D, _, P, _ = pw.shape
+        if D != 64 * num_heads:
+            raise RFError(f"HipClipVisionEncoder: hidden {D} with {num_heads} heads: the attention kernel is built for a head dim of 64")
+        T = sd["embeddings.position_embedding.weight"].shape[0]
+        g = int(round(math.sqrt(T - 1)))
+        if g * g + 1 != T:
+            raise RFError(f"HipClipVisionEncoder: {T} positions is not a square grid + class token")
+        self.device, self.heads, self.hidden, self.patch, self.image_size = device, num_heads, D, P, g * P
+        self.tokens, self.s_pad, self.k_pad = T, _pad32(T), (3 * P * P + 63) // 64 * 64
+        self.proj_dim = sd["visual_projection.weight"].shape[0]
+        k = self._k = _Keep(device)
+        f = lambda t: t.detach().float()  # noqa: E731
+        self._layers = _clip_layers(k, sd, n_layers)
+        wpad = torch.zeros(D, self.k_pad)
+        wpad[:, : 3 * P * P] = f(pw).reshape(D, 3 * P * P).cpu()
+        mask = torch.zeros(self.s_pad, self.s_pad, device=device)
+        mask[:, T:] = float("-inf")
+        self._mask = mask.contiguous()
+        w = self._w = L.rf_clip_vision_weights()
+        w.layers, w.hidden, w.heads, w.inter = n_layers, D, num_heads, sd["encoder.layers.0.mlp.fc1.weight"].shape[0]
+        w.image_size, w.patch, w.proj_dim, w.mask_S, w.eps = self.image_size, P, self.proj_dim, self.s_pad, eps
+        w.patch_w, w.class_embed, w.pos_embed = k.t(wpad), k.t(sd["embeddings.class_embedding"]), k.t(sd["embeddings.position_embedding.weight"])
+        w.pre_ln_scale, w.pre_ln_shift = k.t(f(sd["pre_layrnorm.weight"]) - 1.0), k.t(sd["pre_layrnorm.bias"])
+        w.post_ln_scale, w.post_ln_shift = k.t(f(sd["post_layernorm.weight"]) - 1.0), k.t(sd["post_layernorm.bias"])
+        w.proj, w.mask = k.t(sd["visual_projection.weight"]), self._mask.data_ptr()
+        w.layer = C.cast(self._layers, C.POINTER(L.rf_clip_layer))
+        self._ws = _Workspace(device)
+
+    def alloc_patches(self, n: int) -> torch.Tensor:
+        """im2col patch rows of n images [n, (size / patch)^2, K_pad] bf16 (what preprocess writes and encode reads)."""
+        g = self.image_size // self.patch
+        return torch.empty(n, g * g, self.k_pad, dtype=BF, device=self.device)
+
+    def preprocess(self, img: torch.Tensor, strides: Tuple[int, int, int, int], a: float, b: float, out: torch.Tensor, H: int, W: int,
+                   n: int = 1) -> torch.Tensor:
+        """rf_clip_preprocess of n images read through element strides (image, row, pixel, channel) from `img` (bf16, on the device;
+        its data pointer is image 0, row 0, pixel 0, channel 0) into `out` (alloc_patches rows): level = rint(255 clamp(a v + b, 0, 1)),
+        then CLIPImageProcessor's resize / crop / normalise."""
+        if not (img.is_cuda and out.is_cuda) or img.dtype != BF:
+            raise RFError("HipClipVisionEncoder.preprocess: needs bf16 tensors on the device")
+        si, sr, sp, sc = (int(s) for s in strides)
+        L.check(L.load().rf_clip_preprocess(img.data_ptr(), si, sr, sp, sc, n, H, W, a, b, self.image_size, self.patch, out.data_ptr(), stream_ptr()),
+                "rf_clip_preprocess")
+        return out
+
+    def preprocess_levels(self, levels: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[B, 3, H, W] (or [3, H, W]) 8-bit levels (any dtype holding 0 .. 255, e.g. a PNG's uint8) -> patch rows [B, np, K_pad]."""
+        x = levels[None] if levels.dim() == 3 else levels
+        x = x.to(self.device, BF).contiguous()                          # integers <= 256 are exact in bf16
+        B, _, H, W = x.shape
+        out = self.alloc_patches(B) if out is None else out
+        return self.preprocess(x, (3 * H * W, W, 1, H * W), 1.0 / 255.0, 0.0, out, H, W, B)
+
+    @torch.no_grad()
+    def encode(self, patches: torch.Tensor) -> torch.Tensor:
+        """patch rows [B, np, K_pad] -> image_embeds [B, projection_dim] bf16 (up to 64 images per launch sequence)."""
+        if not patches.is_cuda:
+            raise RFError("HipClipVisionEncoder.encode: patches are on the CPU; the HIP path has no CPU fallback")
+        B = patches.shape[0]
+        lib, w = L.load(), self._w
+        patches = patches.contiguous()
+        out = torch.empty(B, self.proj_dim, dtype=BF, device=self.device)
+        for b0 in range(0, B, self.MAX_BATCH):
+            nb = min(self.MAX_BATCH, B - b0)
+            ws = self._ws.get(lib.rf_clip_vision_workspace_bytes(C.byref(w), nb))
+            L.check(lib.rf_clip_vision_encode(C.byref(w), patches[b0].data_ptr(), nb, out[b0].data_ptr(), C.byref(ws), stream_ptr()),
+                    "rf_clip_vision_encode")
+        return out
+
+
+def clip_score(image_embeds: torch.Tensor, text_embed: torch.Tensor, logit_scale: float) -> torch.Tensor:
+    """rf_clip_score: exp(logit_scale) * cos(image_embeds[b], text_embed) -> f32 [B] on the device."""
+    img = image_embeds.to(BF).contiguous()
+    txt = text_embed.reshape(-1).to(BF).contiguous()
+    B, P = img.shape
+    if txt.numel() != P or not (img.is_cuda and txt.is_cuda):
+        raise RFError(f"clip_score: image embeds {tuple(img.shape)} vs text embed {tuple(text_embed.shape)} (both on the device)")
+    out = torch.empty(B, dtype=torch.float32, device=img.device)
+    if B:
+        L.check(L.load().rf_clip_score(img.data_ptr(), txt.data_ptr(), float(logit_scale), out.data_ptr(), B, P, stream_ptr()), "rf_clip_score")
+    return out
 
 
 class HipTextEncoders:

@@ -189,7 +189,9 @@ class HipVAE:
         return ws
 
     @torch.no_grad()
-    def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None):
+    def decode_halo(self, z: torch.Tensor) -> List[torch.Tensor]:
+        """rf_vae_decode's own output per image: zero-halo NHWC [(H + 2), (W + 2), conv_out.cout] bf16, of which the interior's channels
+        0 .. out_channels - 1 are the image (what decode() returns, copied to NCHW).  The CLIP verifier reads it in place."""
         if not z.is_cuda:
             raise RFError("HipVAE.decode: tensor is on the CPU; the HIP path has no CPU fallback")
         B, Cz, h, wd = z.shape
@@ -202,7 +204,12 @@ class HipVAE:
             zp[1:-1, 1:-1, :Cz] = z[b].to(BF).permute(1, 2, 0)
             out = torch.empty(H + 2, W + 2, w.conv_out.cout, dtype=BF, device=z.device)
             L.check(lib.rf_vae_decode(C.byref(w), zp.data_ptr(), h, wd, out.data_ptr(), C.byref(ws), stream_ptr()), "rf_vae_decode")
-            outs.append(out[1:-1, 1:-1, : self.config["out_channels"]].permute(2, 0, 1))
+            outs.append(out)
+        return outs
+
+    @torch.no_grad()
+    def decode(self, z: torch.Tensor, return_dict: bool = True, generator=None):
+        outs = [out[1:-1, 1:-1, : self.config["out_channels"]].permute(2, 0, 1) for out in self.decode_halo(z)]
         y = torch.stack(outs).contiguous()
         return DecoderOutput(y) if return_dict else (y,)
 

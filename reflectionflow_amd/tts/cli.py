@@ -54,13 +54,19 @@ def main(mode: str, argv=None):
     search.bind_host_threads_to_gpu_numa_node(dev.index)
     pipe = runner.build_pipeline(config, dev, synthetic=args.synthetic, small=args.small)
     os.makedirs(args.output_dir, exist_ok=True)
+    kw = {}
+    if mode == "reflection" and config.get("verifier_args", {}).get("name") == "clip":
+        # verifier_args = {"name": "clip", "clip_model_path": DIR}: the on-device CLIP-score verifier (tts/clip_verifier.py)
+        from .clip_verifier import build_from_config
+        v = build_from_config(config, pipe, synthetic=args.synthetic, small=args.small)
+        kw = dict(score_batch=v.score_batch, score_images=v.score_images)
     if mode == "reflection" and args.imgpath:
         # tts_reflectionflow.py:535-565: prompts and the round-1 pool come from the --imgpath tree (one folder per prompt with
         # metadata.jsonl + samples/), i.e. from a tts_t2i_noise_scaling output directory
         return runner.run_reflection_search(config, None, args.output_dir, pipe, shard, start_index=args.start_index,
-                                            imgpath=args.imgpath)
+                                            imgpath=args.imgpath, **kw)
     with open(args.meta_path) as fp:
         metadatas = [json.loads(line) for line in fp]
     metadatas = metadatas[args.start_index:] if args.end_index == -1 else metadatas[args.start_index:args.end_index]
     prompts = [m["prompt"] for m in metadatas]
-    return MODES[mode](config, prompts, args.output_dir, pipe, shard, start_index=args.start_index, metadatas=metadatas)
+    return MODES[mode](config, prompts, args.output_dir, pipe, shard, start_index=args.start_index, metadatas=metadatas, **kw)

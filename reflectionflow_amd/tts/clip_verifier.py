@@ -1,0 +1,217 @@
+"""On-device CLIP-score verifier for the reflection search.
+
+The verifier is transformers' `CLIPModel` (clip-vit-large-patch14 layout) applied to what the reference's verifier reads -- the
+candidate's saved 8-bit PNG -- and scored against the ORIGINAL prompt, as the reference scores every round
+(tts_reflectionflow.py:157-170, 345-352):
+
+    score = exp(logit_scale) * cos(visual_projection(ViT(CLIPImageProcessor(png))), text_projection(CLIPTextModel(prompt).pooled))
+
+i.e. the diagonal of HF's `logits_per_image`.  A scalar metric: labels are 1 for every candidate and the kind "clip" sorts with
+`search.scalar_sort_key` (descending score, index tie-break), as the reference's scalar ("openai") branch.
+
+The image side never leaves the device: HIP VAE decode -> rf_clip_preprocess (reads the decoder's zero-halo NHWC output in place)
+-> rf_clip_vision_encode (one call per rank and round) -> rf_clip_score -> the runner's {f32, i32} all-gather.  An `--imgpath`
+pool (PNG files) goes through the same kernels from its uint8 levels, so a PNG and the latents it was written from score
+bit-identically.  The text embedding (HIP CLIP text tower + text_projection GEMM) is cached per prompt.
+
+Not done here: sharing one VAE decode between the runner's `_save` (PNG) and the verifier -- each candidate is decoded twice.
+"""
+from __future__ import annotations
+
+import json
+import math
+import os
+from typing import Callable, Dict, List, Sequence
+
+import torch
+
+from .. import ops
+from ..flux.text_hip import HipClipTextEncoder, HipClipVisionEncoder, clip_score
+from ..ops import RFError
+
+# openai/clip-vit-large-patch14
+VIT_L14 = dict(text=dict(vocab=49408, hidden=768, heads=12, inter=3072, layers=12, max_pos=77),
+               vision=dict(hidden=1024, heads=16, inter=4096, layers=24, image_size=224, patch=14), projection_dim=768)
+# --synthetic --small
+TINY = dict(text=dict(vocab=512, hidden=128, heads=2, inter=256, layers=2, max_pos=77),
+            vision=dict(hidden=128, heads=2, inter=256, layers=2, image_size=224, patch=14), projection_dim=64)
+
+
+class ClipScoreVerifier:
+    """`score_batch(latents [n, S, 64], seeds, prompt) -> (f32 [n], i32 [n])` and `score_images(paths, prompt)` for
+    runner.run_reflection_search.  `clip_state_dict`: an HF CLIPModel state dict (`text_model.*`, `vision_model.*`,
+    `text_projection.weight`, `visual_projection.weight`, `logit_scale`); `tokenize(prompts) -> ids [B, L]` (CLIP BPE ids, EOS the
+    largest id for the legacy eos_token_id = 2 config); height / width: the candidates' image size."""
+
+    def __init__(self, pipe, clip_state_dict: Dict[str, torch.Tensor], tokenize: Callable[[List[str]], torch.Tensor], height: int, width: int,
+                 eos_token_id: int = 2, eps: float = 1e-5):
+        from ..flux.vae_hip import HipVAE
+        if pipe.vae is None:
+            raise RFError("ClipScoreVerifier: the pipeline has no VAE -- the verifier scores decoded images (load a pipeline with a vae/ "
+                          "directory, or FluxPipeline.synthetic(..., with_vae=True))")
+        if not isinstance(pipe.vae, HipVAE):
+            raise RFError("ClipScoreVerifier: the pipeline's VAE is not the HIP VAE; call pipe.enable_hip_vae() first")
+        self.pipe, self.height, self.width, self._tokenize = pipe, int(height), int(width), tokenize
+        sd = clip_state_dict
+        dev = pipe.device
+        text = {k[len("text_model."):]: v for k, v in sd.items() if k.startswith("text_model.")}
+        vision = {k: v for k, v in sd.items() if k.startswith("vision_model.") or k == "visual_projection.weight"}
+        if not text or not vision or "text_projection.weight" not in sd or "logit_scale" not in sd:
+            raise RFError("ClipScoreVerifier: needs a CLIPModel state dict (text_model.*, vision_model.*, text/visual_projection, logit_scale)")
+        self.text = HipClipTextEncoder(text, text["embeddings.token_embedding.weight"].shape[1] // 64, dev, eos_token_id=eos_token_id, eps=eps)
+        self.vision = HipClipVisionEncoder(vision, vision["vision_model.embeddings.patch_embedding.weight"].shape[0] // 64, dev, eps=eps)
+        self.text_projection = sd["text_projection.weight"].detach().to(dev, torch.bfloat16).contiguous()
+        self.logit_scale = float(sd["logit_scale"].float())
+        self._text_cache: Dict[str, torch.Tensor] = {}
+
+    # ---- text side -----------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def text_embed(self, prompt: str) -> torch.Tensor:
+        """text_projection(CLIPTextModel(prompt).pooler_output) [projection_dim] bf16, cached per prompt."""
+        if prompt not in self._text_cache:
+            ids = torch.as_tensor(self._tokenize([prompt])).to(self.pipe.device)
+            pooled = self.text.encode(ids)[1]
+            emb = ops.linear(pooled.contiguous(), self.text_projection)[0]
+            if len(self._text_cache) >= 64:
+                self._text_cache.pop(next(iter(self._text_cache)))
+            self._text_cache[prompt] = emb
+        return self._text_cache[prompt]
+
+    # ---- image side ----------------------------------------------------------------------------------------------------------
+    def _decode_into(self, latents: torch.Tensor, patches: torch.Tensor, row: int) -> None:
+        """packed latents [1, S, 64] -> HIP VAE decode (the runner's `_save` arithmetic) -> patch rows of image `row`."""
+        pipe = self.pipe
+        z = pipe._unpack_latents(latents, self.height, self.width, pipe.vae_scale_factor)
+        z = z / pipe.vae.config.scaling_factor + pipe.vae.config.shift_factor
+        out = pipe.vae.decode_halo(z)[0]                                   # [(H + 2), (W + 2), cout], image at the interior, channels 0..2
+        Hp, Wp, cout = out.shape
+        interior = out[1:, 1:]                                              # data pointer at (row 1, pixel 1, channel 0)
+        self.vision.preprocess(interior, (0, Wp * cout, cout, 1), 0.5, 0.5, patches[row:row + 1], Hp - 2, Wp - 2)
+
+    @torch.no_grad()
+    def score_batch(self, latents: torch.Tensor, seeds: Sequence[int], prompt: str):
+        """This rank's candidates of a round: packed latents [n, S, 64] -> (scores f32 [n], labels i32 [n]) on the device; one vision
+        call for all n."""
+        n = latents.shape[0]
+        patches = self.vision.alloc_patches(n)
+        for b in range(n):
+            self._decode_into(latents[b:b + 1], patches, b)
+        return self._score(patches, prompt)
+
+    score_batch.wants_prompt = True           # runner.bind_prompt hands over the original prompt
+
+    @torch.no_grad()
+    def score_images(self, paths: Sequence[str], prompt: str):
+        """An `--imgpath` pool: PNG files (their uint8 levels) or the runner's `.pt` packed latents -> (f32 [n], i32 [n])."""
+        patches = self.vision.alloc_patches(len(paths))
+        for b, p in enumerate(paths):
+            if p.endswith(".pt"):
+                self._decode_into(torch.load(p).to(self.pipe.device, self.pipe.dtype), patches, b)
+                continue
+            import numpy as np
+            from PIL import Image
+            arr = np.asarray(Image.open(p).convert("RGB"))                 # [H, W, 3] uint8: the levels the PNG holds
+            lv = torch.from_numpy(arr.copy()).to(self.pipe.device).permute(2, 0, 1)
+            self.vision.preprocess_levels(lv, out=patches[b:b + 1])
+        return self._score(patches, prompt)
+
+    def _score(self, patches: torch.Tensor, prompt: str):
+        n = patches.shape[0]
+        dev = self.pipe.device
+        if n == 0:
+            return torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+        emb = self.vision.encode(patches)
+        scores = clip_score(emb, self.text_embed(prompt), self.logit_scale)
+        return scores, torch.ones(n, dtype=torch.int32, device=dev)
+
+
+# ---- synthetic model + tokenizer (no checkpoint offline) ------------------------------------------------------------------------
+def synthetic_clip_state(cfg: dict = VIT_L14, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """A seeded random-init HF CLIPModel state dict of the given geometry (fp32, CPU): weights N(0, 1/fan_in) (q / k x 2 so that
+    attention is not uniform), LayerNorm weights 1 + N(0, 0.1^2), biases N(0, 0.1^2), embeddings N(0, 0.2^2) / class N(0, 0.5^2),
+    logit_scale = log(1 / 0.07) (CLIP's init)."""
+    t, v, P = cfg["text"], cfg["vision"], cfg["projection_dim"]
+    shapes = {"text_model.embeddings.token_embedding.weight": (t["vocab"], t["hidden"]),
+              "text_model.embeddings.position_embedding.weight": (t["max_pos"], t["hidden"]),
+              "text_model.final_layer_norm.weight": (t["hidden"],), "text_model.final_layer_norm.bias": (t["hidden"],),
+              "vision_model.embeddings.class_embedding": (v["hidden"],),
+              "vision_model.embeddings.patch_embedding.weight": (v["hidden"], 3, v["patch"], v["patch"]),
+              "vision_model.embeddings.position_embedding.weight": ((v["image_size"] // v["patch"]) ** 2 + 1, v["hidden"]),
+              "vision_model.pre_layrnorm.weight": (v["hidden"],), "vision_model.pre_layrnorm.bias": (v["hidden"],),
+              "vision_model.post_layernorm.weight": (v["hidden"],), "vision_model.post_layernorm.bias": (v["hidden"],),
+              "text_projection.weight": (P, t["hidden"]), "visual_projection.weight": (P, v["hidden"])}
+    for tower, c in (("text_model", t), ("vision_model", v)):
+        D, F = c["hidden"], c["inter"]
+        for i in range(c["layers"]):
+            p = f"{tower}.encoder.layers.{i}."
+            for x in ("q_proj", "k_proj", "v_proj", "out_proj"):
+                shapes[p + f"self_attn.{x}.weight"] = (D, D)
+                shapes[p + f"self_attn.{x}.bias"] = (D,)
+            for nrm in ("layer_norm1", "layer_norm2"):
+                shapes[p + nrm + ".weight"] = (D,)
+                shapes[p + nrm + ".bias"] = (D,)
+            shapes[p + "mlp.fc1.weight"], shapes[p + "mlp.fc1.bias"] = (F, D), (F,)
+            shapes[p + "mlp.fc2.weight"], shapes[p + "mlp.fc2.bias"] = (D, F), (D,)
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for k in sorted(shapes):
+        x = torch.randn(shapes[k], generator=g)
+        if "norm" in k and k.endswith(".weight") or "layrnorm.weight" in k:
+            x = 1.0 + 0.1 * x
+        elif k.endswith(".bias"):
+            x = 0.1 * x
+        elif "position_embedding" in k or "token_embedding" in k:
+            x = 0.2 * x
+        elif k.endswith("class_embedding"):
+            x = 0.5 * x
+        else:
+            fan_in = math.prod(shapes[k][1:])
+            x = x * fan_in ** -0.5 * (2.0 if ("q_proj" in k or "k_proj" in k) else 1.0)
+        sd[k] = x
+    sd["logit_scale"] = torch.tensor(math.log(1 / 0.07))
+    return sd
+
+
+def synthetic_tokenize(vocab: int, length: int = 77) -> Callable[[List[str]], torch.Tensor]:
+    """Deterministic stand-in for CLIP's BPE (its vocabulary files are not shipped): BOS = vocab - 2, one id per UTF-8 byte
+    (3 + byte % (vocab - 5)), EOS = vocab - 1 (the largest id, where the legacy config pools), padded with EOS to `length`."""
+    def tokenize(prompts: List[str]) -> torch.Tensor:
+        out = torch.full((len(prompts), length), vocab - 1, dtype=torch.int64)
+        for i, p in enumerate(prompts):
+            ids = [vocab - 2] + [3 + b % (vocab - 5) for b in p.encode("utf-8")][: length - 2] + [vocab - 1]
+            out[i, : len(ids)] = torch.tensor(ids)
+        return out
+    return tokenize
+
+
+def load_clip_dir(path: str):
+    """An HF CLIPModel directory: config.json + model.safetensors + tokenizer files -> (state dict, tokenize, eos_token_id)."""
+    from safetensors.torch import load_file
+    from transformers import CLIPTokenizer
+    with open(os.path.join(path, "config.json")) as f:
+        cfg = json.load(f)
+    sd = load_file(os.path.join(path, "model.safetensors"))
+    tok = CLIPTokenizer.from_pretrained(path, local_files_only=True)
+
+    def tokenize(prompts: List[str]) -> torch.Tensor:
+        return tok(list(prompts), padding="max_length", max_length=77, truncation=True, return_tensors="pt")["input_ids"]
+    return sd, tokenize, int(cfg.get("text_config", {}).get("eos_token_id", 2))
+
+
+def build_from_config(config: dict, pipe, synthetic: bool = False, small: bool = False) -> ClipScoreVerifier:
+    """The verifier `verifier_args = {"name": "clip", "clip_model_path": DIR}` names; with `synthetic`, a seeded random-init CLIP of
+    ViT-L/14 geometry (TINY with `small`) and the synthetic tokenizer.  Switches the pipeline's VAE to the HIP path."""
+    va, pa = config.get("verifier_args", {}), config["pipeline_args"]
+    if pipe.vae is None:
+        raise RFError("the CLIP verifier needs a pipeline with a VAE")
+    pipe.enable_hip_vae()
+    if synthetic:
+        cfg = TINY if small else VIT_L14
+        seed = int(va.get("seed", 0))
+        sd, tok, eos = synthetic_clip_state(cfg, seed), synthetic_tokenize(cfg["text"]["vocab"]), 2
+    else:
+        if not va.get("clip_model_path"):
+            raise RFError('verifier_args.name == "clip" needs verifier_args.clip_model_path (an HF CLIPModel directory)')
+        sd, tok, eos = load_clip_dir(va["clip_model_path"])
+    return ClipScoreVerifier(pipe, sd, tok, pa["height"], pa["width"], eos_token_id=eos)
+

@@ -19,6 +19,7 @@ function of (prompt index, round, candidate), so results do not depend on the wo
 """
 from __future__ import annotations
 
+import functools
 import json
 import os
 from typing import Dict, List, Optional
@@ -45,7 +46,10 @@ def build_pipeline(config: dict, device, synthetic: bool = False, small: bool = 
     if synthetic:
         cfg = dict(num_layers=2, num_single_layers=2, num_attention_heads=2, joint_attention_dim=256,
                    pooled_projection_dim=64) if small else None
-        pipe = FluxPipeline.synthetic(cfg, seed=0, torch_dtype=dtype, device=device)
+        # the CLIP verifier scores decoded images: a random-init VAE comes with it (the small one: 8x, channels the HIP VAE takes)
+        with_vae = config.get("verifier_args", {}).get("name") == "clip"
+        vcfg = dict(block_out_channels=(64, 64, 128, 128), norm_num_groups=32, mid_block_add_attention=False) if small else None
+        pipe = FluxPipeline.synthetic(cfg, seed=0, torch_dtype=dtype, device=device, with_vae=with_vae, vae_config=vcfg)
     else:
         pipe = FluxPipeline.from_pretrained(pa["pretrained_model_name_or_path"], torch_dtype=dtype,
                                             cache_dir=pa.get("cache_dir") or None).to(device)
@@ -227,7 +231,9 @@ def run_reflection_search(config: dict, prompts: Optional[List[str]], output_dir
                                         round 1), evaluations (JSON strings), search_round)
       refine(ctx, reflections) -> List[str]
     `score_batch(latents [n, S, 64], seeds) -> (f32 [n], i32 [n])` scores generated candidates on the device (one call per
-    round and rank); `score_images(paths, prompt) -> (f32, i32)` scores an `--imgpath` pool.
+    round and rank); `score_images(paths, prompt) -> (f32, i32)` scores an `--imgpath` pool.  A `score_batch` that carries
+    `wants_prompt = True` (tts/clip_verifier.py) is called as `score_batch(latents, seeds, prompt=<the ORIGINAL prompt>)`: the
+    reference scores every round against it (tts_reflectionflow.py:157-170, 345-352), not against the reflected prompts.
 
     Deliberate deviations: the reference's `generate` call passes neither `latents`,
     `num_inference_steps` nor `guidance_scale` (so 28 steps / 3.5 / global-RNG noise apply and the `get_noises` seeds only
@@ -315,7 +321,7 @@ def run_reflection_search(config: dict, prompts: Optional[List[str]], output_dir
                                latents=noise, model_config=model_cfg, default_lora=True, output_type="latent").images
                 _save(os.path.join(outpath, subdir, f"{rnd}_round@{seed}"), lat, pipe, H, W)
                 local[i] = lat
-            scores = _score_local(shard, N, mine, local, seeds, verifier, score_batch)
+            scores = _score_local(shard, N, mine, local, seeds, verifier, bind_prompt(score_batch, prompt))
             ext = ".png" if (pipe.vae is not None and pipe.image_processor is not None) else ".pt"
             names = [f"{subdir}/{rnd}_round@{s}{ext}" for s in seeds]
             return seeds, names, scores, local
@@ -411,6 +417,14 @@ def run_reflection_search(config: dict, prompts: Optional[List[str]], output_dir
     if shard.world_size > 1:
         torch.distributed.barrier()
     return all_logs
+
+
+def bind_prompt(score_batch, prompt: str):
+    """`score_batch` with the prompt bound when it asks for one (`wants_prompt`, e.g. ClipScoreVerifier.score_batch); any other
+    callable -- the two-argument contract, the stub, None -- is returned as it is."""
+    if score_batch is not None and getattr(score_batch, "wants_prompt", False):
+        return functools.partial(score_batch, prompt=prompt)
+    return score_batch
 
 
 def _evaluation(name: str, score, scalar: bool) -> dict:
