@@ -31,7 +31,15 @@
 #include <type_traits>
 #include <stdlib.h>
 
+// RF_PP3_ASM (default 1): gemm_mainloop_pp3_m16 runs its steady-state K-tiles through the hoisted tile_s body with hand-placed
+// LDS-DMA; -DRF_PP3_ASM=0 builds the plain C++ loop (same results bit for bit; the A/B baseline and the readable schedule).
+#ifndef RF_PP3_ASM
+#define RF_PP3_ASM 1
+#endif
+
 namespace rf {
+
+typedef __attribute__((address_space(3))) char lds_char;
 
 struct KSegDev {
   const bf16_t* A; int64_t lda;
@@ -871,6 +879,7 @@ __device__ __forceinline__ void gemm_mainloop_pp2_m16(const GemmGroupDev& G, con
 // THE SHIPPED bf16 LOOP (gemm_bf16_pp16e_kernel; the stream-K kernel's EVEN form): the evenly loaded 6/6/6/6 + 2/2/2/2 ping-pong
 // schedule on 16x16x32 MFMAs: the k-step-0 fragments of column tiles 0, 1 of each W half are read one phase early (e0 / e1), the other six
 // share one register set m; a phase starts with the four MFMAs that need only the early pair.
+template <bool STEADY>   // STEADY: the steady-state K-tiles go through tile_s (RF_PP3_ASM); false: every K-tile goes through tile()
 __device__ __forceinline__ void gemm_mainloop_pp3_m16(const GemmGroupDev& G, const int N, const int m0, const int n0, const int kt_begin,
                                                   const int nk, f32x4 (&acc)[4][8], char* smem, const int w, const int lane) {
   constexpr int ESZ = 2;  // bytes per element
@@ -882,8 +891,7 @@ __device__ __forceinline__ void gemm_mainloop_pp3_m16(const GemmGroupDev& G, con
 
   // staging geometry: DMA instruction i (0,1) of wave w fills local rows (i*8 + w)*8 + lane/8 of a half-tile;
   // local row lr of A_s is tile row (lr>>5)*64 + s*32 + (lr&31), of B_s tile column (lr>>6)*128 + s*64 + (lr&63)
-  const int r8 = lane >> 3;
-  const uint32_t chunk_b = (uint32_t)(((lane & 7) ^ (((w & 1) << 2) + (lane >> 4))) * 16);  // swizzled 16-byte chunk
+  // (r8 = lane >> 3 and the swizzled 16-byte chunk chunk_b are formed in load_seg)
   // K-tile cursors of the tiles being staged (c1 = tile t+1, c2 = tile t+2): segment, tile-in-segment and the
   // segment's buffer resources / row pitches in SGPRs (re-loaded only when a cursor crosses a segment boundary)
   // (the per-lane byte offsets row * pitch + chunk are formed HERE, once per segment: in the loop they were two
@@ -893,6 +901,12 @@ __device__ __forceinline__ void gemm_mainloop_pp3_m16(const GemmGroupDev& G, con
     const KSegDev& S = G.seg[c.seg];
     c.nk = S.nk; c.A = RF_MAKE_RSRC(S.A); c.W = RF_MAKE_RSRC(S.W);
     const uint32_t lda2 = (uint32_t)(S.lda * ESZ), ldw2 = (uint32_t)(S.ldw * ESZ);
+    // STEADY: the lane index comes from an opaque mbcnt, so the clamped rows below are re-derived per segment instead of living in
+    // seven VGPRs across the loop: with the steady-state body beside tile() they do not fit the 256-VGPR budget (they spilled)
+    int ln = lane;
+    if constexpr (STEADY) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+    const int r8 = ln >> 3;
+    const uint32_t chunk_b = (uint32_t)(((ln & 7) ^ (((w & 1) << 2) + (ln >> 4))) * 16);  // swizzled 16-byte chunk
     // (rows are re-derived here, once per segment, instead of living in eight registers across the loop)
 #pragma unroll
     for (int sb = 0; sb < 2; ++sb)
@@ -1051,9 +1065,96 @@ __device__ __forceinline__ void gemm_mainloop_pp3_m16(const GemmGroupDev& G, con
     next(c1);
     next(c2);
   };
+  if constexpr (STEADY) {
+  // steady state: a K-tile t with t + 2 < nk whose two staging cursors c1 (tile t+1) and c2 (tile t+2) lie in one K segment.  Such
+  // tiles run in pairs through tile_s below: no more1 / more2 / next() per tile (the range of steady tiles is computed here, once
+  // per run), the K offset advances in an SGPR, and the LDS-DMA pieces are hand-placed asm with M0 advanced behind each piece.
+  // The reads, MFMAs, waits and barriers are exactly tile()'s, so the result is bit-identical to the C++ body (RF_PP3_ASM=0).
+  //
+  // LDS byte address of DMA piece 0 of stage(kind, ., buf), relative to this wave's slice (smem + w * 1024); piece 1 is 8192 above
+  constexpr auto dst = [](int kind, int buf) { return buf * BUF + kind * HT; };
+  // the eight stages of a tile pair in issue order: {kind, buf} of tile t (buffer 0), then of tile t+1 (buffer 1)
+  constexpr int SK[8] = {3, 0, 2, 1, 3, 0, 2, 1}, SB[8] = {1, 0, 0, 0, 0, 1, 1, 1};
+  // M0 runs through the pieces of a pair without ever being re-loaded: piece 0 of stage i, +8192, piece 1, then on to stage i+1
+  auto dma = [&](auto si, const rsrc_t r, const uint32_t (&voff)[2], const uint32_t soff) {
+    constexpr int i = decltype(si)::value, j = (i + 1) & 7;
+    constexpr uint32_t step = (uint32_t)(dst(SK[j], SB[j]) - dst(SK[i], SB[i]) - 8192);
+    asm volatile("buffer_load_dwordx4 %0, %2, %3 offen lds\n\t"
+                 "s_add_u32 m0, m0, 8192\n\t"
+                 "s_nop 0\n\t"                       // SALU write of M0 -> LDS-DMA read of it: one wait state
+                 "buffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
+                 "s_add_u32 m0, m0, %4"
+                 :: "v"(voff[0]), "v"(voff[1]), "s"(r), "s"(soff), "i"(step) : "memory", "scc");
+  };
+  using I0 = std::integral_constant<int, 0>;
+  // one steady K-tile of buffer parity PB (tile() with more1 = more2 = true); k1 / k2: byte offsets of tiles t+1 / t+2 in the segment
+  auto tile_s = [&](auto pb, bf16x8 (&P)[4], bf16x8 (&Q)[4], const uint32_t k1, const uint32_t k2) {
+    constexpr int PB = decltype(pb)::value, S0 = 4 * PB;
+    const char* base = smem + PB * BUF;
+    const char* nbase = smem + (PB ^ 1) * BUF;
+    // ---- p0: B0 main; DMA B1(t+1) ----
+    rdBm(m, base);
+    __builtin_amdgcn_sched_barrier(0);
+    dma(std::integral_constant<int, S0 + 0>(), c1.W, c1.offB[1], k1);
+    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    RF_PP3_BAR();
+    mma16s(0, 0, P, e0, m);
+    RF_PP3_BAR();
+    // ---- p1: A1, B1 early; DMA A0(t+2) ----
+    rdA(Q, base + HT);
+    rdBe(e1, base + HT);
+    __builtin_amdgcn_sched_barrier(0);
+    dma(std::integral_constant<int, S0 + 1>(), c1.A, c1.offA[0], k2);
+    RF_PP3_BAR();
+    mma16s(2, 0, Q, e0, m);
+    asm volatile("" : "+v"(m[0]), "+v"(m[1]), "+v"(m[2]), "+v"(m[3]), "+v"(m[4]), "+v"(m[5]));
+    RF_PP3_BAR();
+    // ---- p2: B1 main; DMA B0(t+2) ----
+    rdBm(m, base + HT);
+    __builtin_amdgcn_sched_barrier(0);
+    dma(std::integral_constant<int, S0 + 2>(), c1.W, c1.offB[0], k2);
+    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    RF_PP3_BAR();
+    mma16s(2, 4, Q, e1, m);
+    asm volatile("" : "+v"(Q[0]), "+v"(Q[1]), "+v"(Q[2]), "+v"(Q[3]));
+    RF_PP3_BAR();
+    // ---- p3: next tile's A0 and B0 early; DMA A1(t+2) ----
+    rdA(Q, nbase);
+    rdBe(e0, nbase);
+    __builtin_amdgcn_sched_barrier(0);
+    dma(std::integral_constant<int, S0 + 3>(), c1.A, c1.offA[1], k2);
+    RF_PP3_BAR();
+    mma16s(0, 4, P, e1, m);
+    asm volatile("" : "+v"(m[0]), "+v"(m[1]), "+v"(m[2]), "+v"(m[3]), "+v"(m[4]), "+v"(m[5]));
+    RF_PP3_BAR();
+  };
+  const uint32_t m0_pair = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uintptr_t)(lds_char*)smem) + w * 1024 + dst(SK[0], SB[0]);
+  for (int t = 0; t < nk; t += 2) {   // t is even here: a pair starts on buffer 0 with X holding its A0 fragments, as tile(t, X, Y)
+    // steady tiles from t on: t' + 2 < nk and c1.kk + (t' - t) + 1 < c1.nk (then c2 = c1 + 1 shares c1's segment and resources)
+    const int steady = min(nk - 2 - t, c1.nk - 1 - c1.kk);
+    if (steady >= 2) {
+      const int pairs = steady >> 1;
+      uint32_t ko = (uint32_t)c1.kk * 128;
+      // M0 is not live across compiler code here: the compiler's own LDS-DMA (tile(), the prologue) sets it per piece
+      asm volatile("s_mov_b32 m0, %0\n\ts_nop 4" :: "s"(m0_pair) : "memory");
+      for (int i = 0; i < pairs; ++i) {
+        tile_s(I0(), X, Y, ko, ko + 128);
+        tile_s(std::integral_constant<int, 1>(), Y, X, ko + 128, ko + 256);
+        ko += 256;
+      }
+      t += 2 * pairs;
+      c1.kk += 2 * pairs;          // stays inside c1's segment (steady <= c1.nk - 1 - c1.kk)
+      c2 = c1;
+      next(c2);                    // may cross into the next segment
+    }
+    tile(t, X, Y);                 // steady <= nk - 2 - t: at least two tiles are left
+    if (t + 1 < nk) tile(t + 1, Y, X);
+  }
+  } else {
   for (int t = 0; t < nk; t += 2) {
     tile(t, X, Y);
     if (t + 1 < nk) tile(t + 1, Y, X);
+  }
   }
 #undef RF_PP3_BAR
   __builtin_amdgcn_s_setprio(0);
@@ -1119,7 +1220,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp16e_kernel(const GemmParams p
   const int m0 = tm * 256, n0 = tn * 256;
   const int nk = G.seg[0].nk + G.seg[1].nk + G.seg[2].nk;
   f32x4 acc[4][8];
-  gemm_mainloop_pp3_m16(G, p.N, m0, n0, 0, nk, acc, smem, w, lane);
+  gemm_mainloop_pp3_m16<RF_PP3_ASM != 0>(G, p.N, m0, n0, 0, nk, acc, smem, w, lane);
   if (p.probe) clk.end(g_clk_probe);
   __syncthreads();  // every wave is done reading the staged operands: the LDS is free
   gemm_epilogue_lds16<2, false>(p, G, acc, m0, n0, (w >> 1) * 64, (w & 1) * 128, lane, smem + w * EPI_REGION);
@@ -1240,7 +1341,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_bf16_sk_kernel(const GemmPar
     const bool g8 = W8 && G.w8;   // mixed-precision launch: multiply chosen per token group
     if constexpr (MI16) {
       if (g8) gemm_mainloop_pp2_m16<W8>(G, p.N, m0, n0, ub - ts, nk_u, acc, smem, w, lane_i);
-      else if constexpr (EVEN && !W8) gemm_mainloop_pp3_m16(G, p.N, m0, n0, ub - ts, nk_u, acc, smem, w, lane_i);
+      else if constexpr (EVEN && !W8) gemm_mainloop_pp3_m16<false>(G, p.N, m0, n0, ub - ts, nk_u, acc, smem, w, lane_i);
       else gemm_mainloop_pp2_m16<false>(G, p.N, m0, n0, ub - ts, nk_u, acc, smem, w, lane_i);
     }
     static_assert(MI16, "librf_flux.so ships the 16x16 MFMA shapes only");
