@@ -73,7 +73,8 @@ struct GemmParams {
   int ksplit, kchunk; float* ws; int64_t ws_slice; int ws_ld;
   float* scratch; int64_t scratch_bytes;  // host side: the caller's scratch as passed (flags + partials)
   int sched, _pad_s;                      // host side: rf_gemm_desc.schedule (rf_gemm_schedule)
-  int probe, _pad_p;                      // block 0 stores its shader-clock probe (rf_gemm_desc.clock_probe, or while a profile is open)
+  int probe;                              // block 0 stores its shader-clock probe (rf_gemm_desc.clock_probe, or while a profile is open)
+  int buf32;                              // every epilogue output / residual / rope table spans < 2^32 - 1 bytes: epi16_interior may run
   GemmGroupDev g[4];
 };
 
@@ -425,11 +426,203 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmParams& p, const Gem
                                                   const int lane, char* region) {
   gemm_epilogue_lds_v<FM, W8>(p, G, Acc32<FM>{acc}, m0, n0, wrow0, wcol0, lane, region);
 }
+
+// ---- kind-specialised interior epilogue of the 16x16x32 kernels ------------------------------------------
+// gemm_epilogue_lds_v tests the epilogue kind and the row / column bounds inside its row loops, and addresses every store with a
+// 64-bit per-lane pointer: ~1500 instructions per wave after the K loop.  A wave whose 64 x 128 sub-tile lies inside G.M and N
+// (every cfg2 tile) instead runs one of the bodies below, picked by one wave-uniform switch: no kind test and no per-row exec mask
+// in the row loops, and stores / residual and rope loads through buffer resources (uniform 64-bit base of the wave's rows in
+// SGPRs, 32-bit per-lane byte offset).  Per element the arithmetic is that of gemm_epilogue_lds_v, in the same order: the
+// results are bit-identical.  Edge waves, split-K partials and launches whose outputs do not fit 32-bit offsets (p.buf32 = 0,
+// decided in build_params) keep gemm_epilogue_lds_v.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define RF_MAKE_RSRC32(p) __builtin_amdgcn_make_buffer_rsrc((void*)(p), 0, -1, 0x00020000)   // num_records 2^32 - 1
+#define RF_BUF_ST128(v, r, off) __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, 0)
+#define RF_BUF_ST64(v, r, off) __builtin_amdgcn_raw_buffer_store_b64(v, r, off, 0, 0)
+#define RF_BUF_LD128(r, off) __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0)
+#else
+#define RF_MAKE_RSRC32(p) 0
+#define RF_BUF_ST128(v, r, off) ((void)(v))
+#define RF_BUF_ST64(v, r, off) ((void)(v))
+#define RF_BUF_LD128(r, off) u32x4{}
+#endif
+enum EpiKind { EK_STORE, EK_GELU, EK_GATE_RES, EK_Q, EK_K, EK_VT };
+
+// mw0 / ncol0: first row / column of the wave's sub-tile; OPT: GATE_RES with a residual, Q / K with fused RMSNorm + RoPE
+template <int FM, bool W8, int EK, bool OPT>
+__device__ __forceinline__ void epi16_interior(const GemmParams& p, const GemmGroupDev& G, Acc16<FM> acc, const int mw0,
+                                               const int ncol0, const int ncol_base, const int head,
+                                               const int lane, char* region) {
+  if constexpr (EK == EK_VT) {
+    // V^T tiles: [head][tok/64][d][64], key position has bits 2,3 swapped; G.tok_offset % 4 == 0, so every 4-key run is
+    // one 8-byte store
+    const rsrc_t rv = RF_MAKE_RSRC32(p.vt + (int64_t)head * (p.s_pad >> 6) * (128 * 64));
+    const int l15 = lane & 15, g = lane >> 4;
+    float bias_v[8], swn[8];   // per column tile jt: hoisted, so the run loop below has no branch
+#pragma unroll
+    for (int jt = 0; jt < 8; ++jt) {
+      const int n = ncol0 + jt * 16 + l15;
+      bias_v[jt] = G.bias != nullptr ? bf2f(G.bias[n]) : 0.f;
+      swn[jt] = W8 ? G.w_scale[n] : 1.f;
+    }
+#pragma unroll
+    for (int jt = 0; jt < 8; ++jt)
+#pragma unroll
+      for (int it = 0; it < 2 * FM; ++it) {   // the run order of Acc16::for_each_run4
+        const int row = it * 16 + 4 * g, col = jt * 16 + l15;
+        float v[4] = {acc.a[it][jt][0], acc.a[it][jt][1], acc.a[it][jt][2], acc.a[it][jt][3]};
+        const int m = mw0 + row;
+        if constexpr (W8) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] *= swn[jt] * G.a_scale[m + e];
+        }
+        const int tok = G.tok_offset + m;
+        const int pos = (tok & 51) | ((tok & 4) << 1) | ((tok & 8) >> 1);
+        u32x2 o;
+        o[0] = pack2(v[0] + bias_v[jt], v[1] + bias_v[jt]);
+        o[1] = pack2(v[2] + bias_v[jt], v[3] + bias_v[jt]);
+        RF_BUF_ST64(o, rv, (uint32_t)((tok >> 6) * (128 * 64) + col * 64 + pos) * 2u);
+      }
+    return;
+  }
+  constexpr bool QK = EK == EK_Q || EK == EK_K;
+  const int q8 = (lane & 15) * 8;  // this lane's 8 consecutive columns
+  const int n = ncol0 + q8;
+  float bias8[8], gate8[8], sw8[8], nw8[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) bias8[e] = 0.f, gate8[e] = 0.f, sw8[e] = 1.f, nw8[e] = 1.f;
+  if constexpr (W8) {
+    const f32x4 s0 = *(const f32x4*)(G.w_scale + n), s1 = *(const f32x4*)(G.w_scale + n + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sw8[e] = s0[e], sw8[e + 4] = s1[e];
+  }
+  if (G.bias != nullptr) unpack8(*(const u32x4*)(G.bias + n), bias8);
+  if constexpr (EK == EK_GATE_RES) unpack8(*(const u32x4*)(G.gate + n), gate8);
+  if constexpr (QK && OPT) unpack8(*(const u32x4*)((EK == EK_Q ? G.norm_q : G.norm_k) + q8), nw8);
+  const int rsub = lane >> 4;      // row within a 4-row read group
+  const int c0 = (lane & 15) * 2;  // first of this lane's two 16-byte chunks
+  // uniform bases of the wave's first row; per lane: row * pitch + column, in bytes
+  const uint32_t ldo = QK ? 128u : (uint32_t)G.ldo, ldr = (uint32_t)G.ldr;
+  const int tok0 = G.tok_offset + mw0;
+  const rsrc_t rdst = QK ? RF_MAKE_RSRC32((EK == EK_Q ? p.q : p.k) + ((int64_t)head * p.s_pad + tok0) * 128)
+                                  : RF_MAKE_RSRC32(G.out + (int64_t)mw0 * G.ldo + (ncol0 - ncol_base));
+  constexpr bool RES = EK == EK_GATE_RES && OPT, ROPE = QK && OPT;   // (no pointer arithmetic on a null table)
+  const rsrc_t rres = RF_MAKE_RSRC32(RES ? G.residual + (int64_t)mw0 * G.ldr + ncol0 : G.residual);
+  const rsrc_t rcos = RF_MAKE_RSRC32(ROPE ? p.rope_cos + (int64_t)tok0 * 128 : p.rope_cos);
+  const rsrc_t rsin = RF_MAKE_RSRC32(ROPE ? p.rope_sin + (int64_t)tok0 * 128 : p.rope_sin);
+
+#pragma unroll
+  for (int i = 0; i < FM; ++i) {
+    acc.stage(i, region, lane);  // registers -> LDS (row-major fp32, padded rows)
+#pragma unroll
+    for (int ib = 0; ib < 2; ++ib) {  // two batches of 4 row groups: bounds the prefetch registers
+      u32x4 resv[4];
+      if constexpr (EK == EK_GATE_RES && OPT) {
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+          const uint32_t r = i * 32 + (ib * 4 + it) * 4 + rsub;
+          resv[it] = RF_BUF_LD128(rres, (r * ldr + q8) * 2u);
+        }
+      }
+#pragma unroll
+      for (int it = 0; it < 4; ++it) {
+        const int row = (ib * 4 + it) * 4 + rsub;
+        const uint32_t r = i * 32 + row;  // row in the wave's sub-tile
+        const f32x4 lo = *(const f32x4*)(region + row * EPI_ROW + c0 * 16);
+        const f32x4 hi = *(const f32x4*)(region + row * EPI_ROW + c0 * 16 + 16);
+        float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        if constexpr (W8) {
+          const float sa = G.a_scale[mw0 + r];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] *= sa * sw8[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += bias8[e];
+        if constexpr (EK == EK_GELU) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] = gelu_tanh(v[e]);
+        } else if constexpr (EK == EK_GATE_RES) {
+          float rr[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) rr[e] = 0.f;
+          if constexpr (OPT) unpack8(resv[it], rr);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] = fmaf(gate8[e], v[e], rr[e]);
+        } else if constexpr (QK) {
+          if constexpr (OPT) {
+            const uint32_t toff = (r * 128 + q8) * 4u;
+            const f32x4 ca = __builtin_bit_cast(f32x4, RF_BUF_LD128(rcos, toff)), cb = __builtin_bit_cast(f32x4, RF_BUF_LD128(rcos, toff + 16));
+            const f32x4 sa = __builtin_bit_cast(f32x4, RF_BUF_LD128(rsin, toff)), sb = __builtin_bit_cast(f32x4, RF_BUF_LD128(rsin, toff + 16));
+            const float cs[8] = {ca[0], ca[1], ca[2], ca[3], cb[0], cb[1], cb[2], cb[3]};
+            const float sn[8] = {sa[0], sa[1], sa[2], sa[3], sb[0], sb[1], sb[2], sb[3]};
+            float ss = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ss = fmaf(v[e], v[e], ss);
+#pragma unroll
+            for (int o = 8; o >= 1; o >>= 1) ss += __shfl_xor(ss, o);
+            const float rs = rsqrtf(fmaf(ss, 1.0f / 128.0f, p.norm_eps));
+#pragma unroll
+            for (int e = 0; e < 8; e += 2) {
+              const float a = v[e] * rs * nw8[e], b = v[e + 1] * rs * nw8[e + 1];
+              v[e] = fmaf(a, cs[e], -(b * sn[e]));
+              v[e + 1] = fmaf(b, cs[e + 1], a * sn[e + 1]);
+            }
+          }
+          if constexpr (EK == EK_Q) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] *= p.q_scale;
+          }
+        }
+        RF_BUF_ST128(pack8(v), rdst, (r * ldo + q8) * 2u);
+      }
+    }
+  }
+}
+
 template <int FM, bool W8 = false>
 __device__ __forceinline__ void gemm_epilogue_lds16(const GemmParams& p, const GemmGroupDev& G, f32x4 (&acc)[2 * FM][8],
                                                     const int m0, const int n0, const int wrow0, const int wcol0,
                                                     const int lane, char* region) {
-  gemm_epilogue_lds_v<FM, W8>(p, G, Acc16<FM>{acc}, m0, n0, wrow0, wcol0, lane, region);
+  int epi = p.epi;
+  int ncol_base = 0;
+  if (epi == RF_EPI_QKV_GELU) {
+    if (n0 >= p.n_split) {
+      epi = RF_EPI_GELU;
+      ncol_base = p.n_split;
+    } else {
+      epi = RF_EPI_QKV;
+    }
+  }
+  const int mw0 = m0 + wrow0, ncol0 = n0 + wcol0;
+  int which = 0, head = 0;
+  if (epi == RF_EPI_QKV) {
+    const int DH = p.heads * 128;
+    which = ncol0 / DH;
+    head = (ncol0 - which * DH) >> 7;
+  }
+  const Acc16<FM> a{acc};
+  // one wave-uniform decision per tile (every operand is a kernel argument or derived from the block / wave index)
+  const bool interior = p.buf32 && p.ksplit <= 1 && mw0 + 32 * FM <= G.M && ncol0 + 128 <= p.N &&
+                        (epi != RF_EPI_QKV || which != 2 || (G.tok_offset & 3) == 0);
+  if (!interior) {
+    gemm_epilogue_lds_v<FM, W8>(p, G, a, m0, n0, wrow0, wcol0, lane, region);
+    return;
+  }
+  switch (epi) {
+    case RF_EPI_STORE: epi16_interior<FM, W8, EK_STORE, false>(p, G, a, mw0, ncol0, ncol_base, head, lane, region); break;
+    case RF_EPI_GELU: epi16_interior<FM, W8, EK_GELU, false>(p, G, a, mw0, ncol0, ncol_base, head, lane, region); break;
+    case RF_EPI_GATE_RES:
+      if (G.residual != nullptr) epi16_interior<FM, W8, EK_GATE_RES, true>(p, G, a, mw0, ncol0, ncol_base, head, lane, region);
+      else epi16_interior<FM, W8, EK_GATE_RES, false>(p, G, a, mw0, ncol0, ncol_base, head, lane, region);
+      break;
+    default:  // RF_EPI_QKV
+      if (which == 2) epi16_interior<FM, W8, EK_VT, false>(p, G, a, mw0, ncol0, ncol_base, head, lane, region);
+      else if (which == 0 && p.rope_cos != nullptr) epi16_interior<FM, W8, EK_Q, true>(p, G, a, mw0, ncol0, ncol_base, head, lane, region);
+      else if (which == 0) epi16_interior<FM, W8, EK_Q, false>(p, G, a, mw0, ncol0, ncol_base, head, lane, region);
+      else if (p.rope_cos != nullptr) epi16_interior<FM, W8, EK_K, true>(p, G, a, mw0, ncol0, ncol_base, head, lane, region);
+      else epi16_interior<FM, W8, EK_K, false>(p, G, a, mw0, ncol0, ncol_base, head, lane, region);
+      break;
+  }
 }
 
 // ---- main loop ----------------------------------------------------------------------------------------
@@ -1161,6 +1354,18 @@ __device__ __forceinline__ void gemm_mainloop_pp3_m16(const GemmGroupDev& G, con
   if (grp == 0) __builtin_amdgcn_s_barrier();  // match group 1's extra barrier
 }
 
+// probe only (rf_debug_clock_probe(2)): when has block 0 / wave 0's part of the tile left the CU?
+__device__ __forceinline__ void epi_probe_end(const GemmParams& p, const int w, const int tid) {
+  if (p.probe && blockIdx.x == 0 && w == 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (tid == 0) {
+      unsigned long long c, r;
+      asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(c), "=s"(r)::"memory");
+      g_clk_probe_epi[0] = c; g_clk_probe_epi[1] = r;
+    }
+  }
+}
+
 // launches on the 16x16 MFMA shapes (gemm_mainloop_pp2_m16): bf16, or W8 = mixed precision per token group
 template <bool W8>
 __device__ __forceinline__ void gemm_pp16_body(const GemmParams& p) {
@@ -1192,14 +1397,7 @@ __device__ __forceinline__ void gemm_pp16_body(const GemmParams& p) {
     __syncthreads();  // every wave is done reading the staged operands: the LDS is free
     gemm_epilogue_lds16<2, false>(p, G, acc, m0, n0, (w >> 1) * 64, (w & 1) * 128, lane, smem + w * EPI_REGION);
   }
-  if (p.probe && blockIdx.x == 0 && w == 0) {   // probe only: when has this wave's part of the tile left the CU?
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (tid == 0) {
-      unsigned long long c, r;
-      asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(c), "=s"(r)::"memory");
-      g_clk_probe_epi[0] = c; g_clk_probe_epi[1] = r;
-    }
-  }
+  epi_probe_end(p, w, tid);
 }
 // bf16 launches, evenly loaded phases (gemm_mainloop_pp3_m16)
 __global__ __launch_bounds__(512) void gemm_bf16_pp16e_kernel(const GemmParams p) {
@@ -1224,6 +1422,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp16e_kernel(const GemmParams p
   if (p.probe) clk.end(g_clk_probe);
   __syncthreads();  // every wave is done reading the staged operands: the LDS is free
   gemm_epilogue_lds16<2, false>(p, G, acc, m0, n0, (w >> 1) * 64, (w & 1) * 128, lane, smem + w * EPI_REGION);
+  epi_probe_end(p, w, tid);
 }
 __global__ __launch_bounds__(512) void gemm_w8_pp16_kernel(const GemmParams p) { gemm_pp16_body<true>(p); }
 
@@ -1718,6 +1917,21 @@ static int build_params(const rf_gemm_desc* d, GemmParams& p, const bool w8 = fa
           (t.residual == nullptr || (aligned16(t.residual) && t.ldr % 8 == 0));
   }
   p.vec_ok = vec ? 1 : 0;
+  // epi16_interior (the 16x16x32 kernels' interior epilogue) addresses outputs, residuals and rope tables as buffer resource
+  // (num_records 2^32 - 1) + 32-bit byte offset.  A launch where any of them spans more than that from its base -- an output
+  // or residual of more than 4 GiB, q / k / V^T or a rope table over too many tokens -- keeps the 64-bit global-address
+  // epilogue (gemm_epilogue_lds_v) on every tile, instead of having the hardware range check drop stores.
+  {
+    constexpr int64_t lim = 0xffffffffll;
+    bool b32 = true;
+    if (qkv) b32 = b32 && (int64_t)d->heads * d->s_pad * 128 * 2 < lim && (int64_t)d->s_pad * 128 * 4 < lim;
+    for (int g = 0; g < ng; ++g) {
+      const GemmGroupDev& t = p.g[g];
+      if (t.out != nullptr) b32 = b32 && ((int64_t)(t.M - 1) * t.ldo + d->N) * 2 < lim && t.ldo >= 0;
+      if (t.residual != nullptr) b32 = b32 && ((int64_t)(t.M - 1) * t.ldr + d->N) * 2 < lim && t.ldr >= 0;
+    }
+    p.buf32 = b32 ? 1 : 0;
+  }
   p.probe = (d->clock_probe != 0 || prof_open()) ? 1 : 0;
   if (w8) {
     RF_REQUIRE(vec, RF_ERR_ALIGN, "rf_gemm_w8a8: needs N %% 8 == 0 and 16-byte aligned outputs / bias / gate / residual");
