@@ -37,7 +37,8 @@ typedef enum rf_status {
 const char* rf_last_error(void);
 /* ABI version: bump on any struct/signature change (v13: rf_attn_bwd_desc.kernel, rf_lora_adamw / rf_lora_prodigy; v14: rf_lora_fuse /
  * rf_lora_unfuse_grads, rf_qkv_train_fwd's forward-only form; v15: rf_lora_clip_grad_norm; v16: the CLIP-score verifier,
- * rf_clip_vision_weights / rf_clip_preprocess / rf_clip_vision_encode / rf_clip_score). */
+ * rf_clip_vision_weights / rf_clip_preprocess / rf_clip_vision_encode / rf_clip_score; v17: the search's on-device round hand-off,
+ * rf_image_levels / rf_pil_resize_to_vae_input). */
 int rf_abi_version(void);
 /* Returns 950 when the library was compiled for gfx950. */
 int rf_target_arch(void);
@@ -525,6 +526,34 @@ int rf_clip_vision_encode(const rf_clip_vision_weights* w, const void* patches, 
 /* scores[b] = exp(logit_scale) * <img_b / |img_b|, txt / |txt|> in fp32 (img [B][P], txt [P] bf16; logit_scale = the model's
  * log-domain parameter); one workgroup per row, fixed reduction order */
 int rf_clip_score(const void* img, const void* txt, float logit_scale, float* scores, int32_t B, int32_t P, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Round hand-off of the reflection search (tts_reflectionflow.py:273-279: a selected candidate's PNG is re-opened,
+ * `resize((condition_size, condition_size))`d with PIL's default filter and VAE-encoded as the next round's "cot" condition).
+ * Both entry points restate host arithmetic bit for bit, so the search's files, scores and latents do not depend on which side
+ * of the bus the boundary runs.  Neither synchronises.
+ * ---------------------------------------------------------------------------------- */
+/* B decoded images -> 8-bit levels [B][H][W][3] (uint8, 4-byte aligned), diffusers' VaeImageProcessor.postprocess in fp32 with one
+ * rounding per step: x = v / 2 + 0.5, clamp to [0, 1], rint(255 x) (half to even).  Image b, row y, pixel x, channel c (0..2) is
+ * img[b * s_img + y * s_row + x * s_pix + c * s_ch] (bf16, element strides, as rf_clip_preprocess: the VAE decoder's zero-halo NHWC
+ * output at its interior).  H, W <= 8192. */
+int rf_image_levels(const void* img, int64_t s_img, int64_t s_row, int64_t s_pix, int64_t s_ch, int32_t B, int32_t H, int32_t W, void* levels,
+                    void* stream);
+/* levels [B][H][W][3] uint8 -> the image Pillow's `Image.resize((w, h))` returns for an RGB image with the default (bicubic) filter,
+ * written twice: out_levels [B][h][w][3] uint8, and out_halo, image b at out_halo + b * s_halo (bf16 elements), the zero-halo NHWC
+ * buffer [(h + 2)][(w + 2)][cin_pad] rf_vae_encode reads: lut[level] in channels 0..2 of the interior, zeros in the halo ring and
+ * the pad channels (anything behind that, e.g. the slack the encoder's first GEMM reads, is the caller's).  lut: 256 bf16 values,
+ * bf16(2 (level / 255) - 1) as the caller's framework rounds it (VaeImageProcessor.preprocess + .to(bf16)).
+ * Pillow's 8-bit resampler is integer arithmetic and is matched exactly: per axis (in -> out), output i reads taps lo[i] ..
+ * lo[i] + n[i] - 1 with the 22-bit coefficients coef[j * out + i] (TAP-major: [k][out] int32, k <= 2 ceil(2 max(in / out, 1)) + 1;
+ * precompute_coeffs + normalize_coeffs_8bpc, built on the host in double: flux/image_hip.py pil_resize_tables) and gives
+ * clip(((1 << 21) + sum level * coef) >> 22, 0, 255); the horizontal pass runs first into an 8-bit image ([B][H][w][3], in
+ * `scratch`, needed only when both axes change), the vertical pass reads it.  An axis whose size does not change is skipped and its
+ * tables may be NULL.  All tables are device arrays; windows are clamped to the image, so a bad table gives wrong pixels, not a
+ * wild access.  Sides <= 8192; cin_pad % 8 == 0; out_halo 16-byte, the level images 4-byte aligned. */
+int rf_pil_resize_to_vae_input(const void* levels, int32_t B, int32_t H, int32_t W, int32_t h, int32_t w, const int32_t* x_lo, const int32_t* x_n,
+                               const int32_t* x_coef, int32_t kx, const int32_t* y_lo, const int32_t* y_n, const int32_t* y_coef, int32_t ky,
+                               const void* lut, void* scratch, void* out_levels, void* out_halo, int64_t s_halo, int32_t cin_pad, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * TRAINING path: backward of the same blocks, for the LoRA reflection tuning of

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librf_flux.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 RF_EPI_STORE, RF_EPI_GELU, RF_EPI_GATE_RES, RF_EPI_QKV, RF_EPI_QKV_GELU = range(5)
 # rf_gemm_schedule (rf_gemm_desc.schedule): how ONE launch is cut into workgroups; AUTO everywhere in the product
@@ -214,6 +214,10 @@ _SIGS = {
     "rf_clip_vision_workspace_bytes": (C.c_int64, [C.POINTER(rf_clip_vision_weights), C.c_int32]),
     "rf_clip_vision_encode": (C.c_int, [C.POINTER(rf_clip_vision_weights), _P, C.c_int32, _P, C.POINTER(rf_workspace), _P]),
     "rf_clip_score": (C.c_int, [_P, _P, C.c_float, _P, C.c_int32, C.c_int32, _P]),
+    # round hand-off of the reflection search (csrc/image_handoff.hip)
+    "rf_image_levels": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "rf_pil_resize_to_vae_input": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32,
+                                             _P, _P, _P, _P, C.c_int64, C.c_int32, _P]),
     # training path
     "rf_qkv_train_fwd": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float,
                                    _P, _P, _P, _P, _P, _P, _P]),

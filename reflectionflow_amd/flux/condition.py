@@ -4,12 +4,17 @@
 
 Also accepts pre-encoded tokens (`tokens=`) so the search runner can hand a candidate's latents to
 the next round without a PNG -> VAE round trip; that is an addition, not a change of the
-reference call sites (tts_reflectionflow.py:273-279 keeps working)."""
+reference call sites (tts_reflectionflow.py:273-279 keeps working).
+
+And the VAE encoder's output for the condition image (`moments=`, [2C, h, w] = mean | logvar on the device): `encode` then only
+draws the posterior sample -- with `self.generator`, exactly as `DiagonalGaussianDistribution.sample` -- and shifts, scales and
+packs as `encode_images`.  The encoder's output is the same for every child of one parent, so the search runner encodes a parent
+once per rank (HipVAE.encode_moments_halo) and every child samples from it with its own generator."""
 from typing import Optional, Tuple
 
 import torch
 
-from .pipeline_tools import encode_images
+from .pipeline_tools import encode_images, tokens_from_posterior
 
 condition_dict = {"depth": 0, "canny": 1, "subject": 4, "coloring": 6, "deblurring": 7, "depth_pred": 8,
                   "fill": 9, "sr": 10, "cartoon": 11, "cot": 12}
@@ -19,14 +24,19 @@ _PASS_THROUGH = ("subject", "fill", "cartoon", "sr", "cot", "depth_pred")
 
 class Condition(object):
     def __init__(self, condition_type: str, raw_img=None, condition=None, mask=None, position_delta=None,
-                 tokens: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None) -> None:
+                 tokens: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None,
+                 moments: Optional[torch.Tensor] = None) -> None:
         self.condition_type = condition_type
         if condition_type not in condition_dict:
             raise NotImplementedError(f"Condition type {condition_type} not implemented")
-        assert raw_img is not None or condition is not None or tokens is not None
+        assert raw_img is not None or condition is not None or tokens is not None or moments is not None
         assert mask is None, "Mask not supported yet"
-        self.tokens, self.ids = tokens, ids
-        if tokens is not None:
+        self.tokens, self.ids, self.moments = tokens, ids, moments
+        if moments is not None:
+            assert tokens is None and raw_img is None and condition is None, "moments= is a form of its own"
+            assert moments.dim() == 3 and moments.shape[0] % 2 == 0, "moments are the encoder's [2C, h, w] output (mean | logvar)"
+            self.condition = None
+        elif tokens is not None:
             assert ids is not None, "pre-encoded condition tokens need their position ids"
             self.condition = None
         elif raw_img is not None:
@@ -66,6 +76,9 @@ class Condition(object):
     def encode(self, pipe, empty: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         if self.tokens is not None:
             tokens, ids = self.tokens, self.ids.clone()
+        elif self.moments is not None:
+            from .vae import DiagonalGaussianDistribution
+            tokens, ids = tokens_from_posterior(pipe, DiagonalGaussianDistribution(self.moments[None]), self.generator)
         else:
             # NB the reference encodes the real condition even when empty=True (condition.py:114-121)
             tokens, ids = encode_images(pipe, self.condition) if self.generator is None else \

@@ -10,7 +10,11 @@ def encode_images(pipeline, images: Tensor, generator=None):
     VAE posterior sample is drawn from."""
     images = pipeline.image_processor.preprocess(images)
     images = images.to(pipeline.device).to(pipeline.dtype)
-    dist = pipeline.vae.encode(images).latent_dist
+    return tokens_from_posterior(pipeline, pipeline.vae.encode(images).latent_dist, generator)
+
+
+def tokens_from_posterior(pipeline, dist, generator=None):
+    """The tail of `encode_images` (pipeline_tools.py:10-30): posterior sample -> shift / scale -> packed tokens + ids."""
     images = dist.sample() if generator is None else dist.sample(generator=generator)
     images = (images - pipeline.vae.config.shift_factor) * pipeline.vae.config.scaling_factor
     images_tokens = pipeline._pack_latents(images, *images.shape)

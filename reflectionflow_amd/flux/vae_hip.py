@@ -213,6 +213,15 @@ class HipVAE:
         y = torch.stack(outs).contiguous()
         return DecoderOutput(y) if return_dict else (y,)
 
+    def _encode_halo(self, xp: torch.Tensor, H: int, W: int) -> torch.Tensor:
+        """rf_vae_encode on one zero-halo NHWC input [(H + 2), (W + 2), conv_in.cin] -> its moments as a [2 * latent, H/8, W/8] view."""
+        lib, w = L.load(), self._enc
+        ws = self._workspace(w, 1, H, W)
+        h, wd = H // self.scale, W // self.scale
+        out = torch.empty(h + 2, wd + 2, w.conv_out.cout, dtype=BF, device=xp.device)
+        L.check(lib.rf_vae_encode(C.byref(w), xp.data_ptr(), H, W, out.data_ptr(), C.byref(ws), stream_ptr()), "rf_vae_encode")
+        return out[1:-1, 1:-1, : 2 * self.config["latent_channels"]].permute(2, 0, 1)
+
     @torch.no_grad()
     def encode_moments(self, x: torch.Tensor) -> torch.Tensor:
         """[B, 3, H, W] in [-1, 1] -> [B, 2 * latent, H/8, W/8] (mean | logvar), bf16."""
@@ -221,17 +230,27 @@ class HipVAE:
         B, Cx, H, W = x.shape
         if H % self.scale or W % self.scale:
             raise RFError(f"HipVAE.encode: image sides must be multiples of {self.scale}, got {H}x{W}")
-        lib, w = L.load(), self._enc
-        ws = self._workspace(w, 1, H, W)
-        h, wd = H // self.scale, W // self.scale
         outs = []
         for b in range(B):
-            xp = _padded_input(H, W, w.conv_in.cin, x.device)
+            xp = _padded_input(H, W, self._enc.conv_in.cin, x.device)
             xp[1:-1, 1:-1, :Cx] = x[b].to(BF).permute(1, 2, 0)
-            out = torch.empty(h + 2, wd + 2, w.conv_out.cout, dtype=BF, device=x.device)
-            L.check(lib.rf_vae_encode(C.byref(w), xp.data_ptr(), H, W, out.data_ptr(), C.byref(ws), stream_ptr()), "rf_vae_encode")
-            outs.append(out[1:-1, 1:-1, : 2 * self.config["latent_channels"]].permute(2, 0, 1))
+            outs.append(self._encode_halo(xp, H, W))
         return torch.stack(outs).contiguous()
+
+    @torch.no_grad()
+    def encode_moments_halo(self, xp: torch.Tensor) -> torch.Tensor:
+        """rf_vae_encode on a caller-built input, without the NCHW -> NHWC copy of encode_moments: xp is ONE image as the zero-halo
+        NHWC buffer [(H + 2), (W + 2), image_pad] bf16 (image in [-1, 1] at the interior's channels 0..2, zero halo ring and pad
+        channels, and 64 zeroed pixels of slack behind it, as image_hip.resize_levels allocates) -> [2 * latent, H/8, W/8]
+        (mean | logvar), bf16: encode_moments(x)[0] of the image it holds."""
+        if not xp.is_cuda or xp.dtype != BF:
+            raise RFError("HipVAE.encode: needs a bf16 tensor on the device; the HIP path has no CPU fallback")
+        if xp.dim() != 3 or xp.shape[2] != self.image_pad or not xp.is_contiguous():
+            raise RFError(f"HipVAE.encode_moments_halo: needs a contiguous [(H + 2), (W + 2), {self.image_pad}] buffer, got {tuple(xp.shape)}")
+        H, W = xp.shape[0] - 2, xp.shape[1] - 2
+        if H % self.scale or W % self.scale:
+            raise RFError(f"HipVAE.encode: image sides must be multiples of {self.scale}, got {H}x{W}")
+        return self._encode_halo(xp, H, W).contiguous()
 
     @torch.no_grad()
     def encode(self, x: torch.Tensor, return_dict: bool = True):

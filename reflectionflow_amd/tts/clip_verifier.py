@@ -14,7 +14,8 @@ The image side never leaves the device: HIP VAE decode -> rf_clip_preprocess (re
 pool (PNG files) goes through the same kernels from its uint8 levels, so a PNG and the latents it was written from score
 bit-identically.  The text embedding (HIP CLIP text tower + text_projection GEMM) is cached per prompt.
 
-Not done here: sharing one VAE decode between the runner's `_save` (PNG) and the verifier -- each candidate is decoded twice.
+The decode is shared with the runner: `score_batch` carries `wants_decoded`, so on the runner's device hand-off path it is given the
+buffers `_save` already decoded (`score_decoded`) and a candidate is decoded once per rank.  Called with latents alone it decodes itself.
 """
 from __future__ import annotations
 
@@ -83,15 +84,23 @@ class ClipScoreVerifier:
         pipe = self.pipe
         z = pipe._unpack_latents(latents, self.height, self.width, pipe.vae_scale_factor)
         z = z / pipe.vae.config.scaling_factor + pipe.vae.config.shift_factor
-        out = pipe.vae.decode_halo(z)[0]                                   # [(H + 2), (W + 2), cout], image at the interior, channels 0..2
+        self._halo_into(pipe.vae.decode_halo(z)[0], patches, row)
+
+    def _halo_into(self, out: torch.Tensor, patches: torch.Tensor, row: int) -> None:
+        """the decoder's output [(H + 2), (W + 2), cout] (image at the interior, channels 0..2), read in place -> patch rows of image `row`."""
         Hp, Wp, cout = out.shape
         interior = out[1:, 1:]                                              # data pointer at (row 1, pixel 1, channel 0)
         self.vision.preprocess(interior, (0, Wp * cout, cout, 1), 0.5, 0.5, patches[row:row + 1], Hp - 2, Wp - 2)
 
     @torch.no_grad()
-    def score_batch(self, latents: torch.Tensor, seeds: Sequence[int], prompt: str):
+    def score_batch(self, latents: torch.Tensor, seeds: Sequence[int], prompt: str, decoded=None):
         """This rank's candidates of a round: packed latents [n, S, 64] -> (scores f32 [n], labels i32 [n]) on the device; one vision
-        call for all n."""
+        call for all n.  `decoded`: the candidates' HipVAE.decode_halo outputs, in row order, if the caller has them (the runner's
+        device hand-off): then nothing is decoded here."""
+        if decoded is not None:
+            if len(decoded) != latents.shape[0]:
+                raise RFError(f"ClipScoreVerifier.score_batch: {latents.shape[0]} candidates but {len(decoded)} decoded buffers")
+            return self.score_decoded(decoded, prompt)
         n = latents.shape[0]
         patches = self.vision.alloc_patches(n)
         for b in range(n):
@@ -99,6 +108,18 @@ class ClipScoreVerifier:
         return self._score(patches, prompt)
 
     score_batch.wants_prompt = True           # runner.bind_prompt hands over the original prompt
+    score_batch.wants_decoded = True          # ... and the runner's device hand-off the buffers it already decoded
+
+    @torch.no_grad()
+    def score_decoded(self, halos, prompt: str):
+        """Candidates already decoded (HipVAE.decode_halo outputs, [(H + 2), (W + 2), cout] each) -> (scores f32 [n], labels i32 [n]):
+        `score_batch` without its decode, the same kernels on the same values."""
+        patches = self.vision.alloc_patches(len(halos))
+        for b, out in enumerate(halos):
+            if out.shape[0] - 2 != self.height or out.shape[1] - 2 != self.width:
+                raise RFError(f"ClipScoreVerifier.score_decoded: buffer {tuple(out.shape)} is not a decoded {self.height}x{self.width} image")
+            self._halo_into(out, patches, b)
+        return self._score(patches, prompt)
 
     @torch.no_grad()
     def score_images(self, paths: Sequence[str], prompt: str):

@@ -16,6 +16,14 @@ the reflection / prompt-refinement LLMs.  They plug in through `score_batch` / `
 Sharding: candidate i of a round runs on rank i % world_size; the collectives are the all-gather of {score, label}
 records and one owners-only all-gather of the parents' latents per round (tts/search.py).  Seeds are a pure
 function of (prompt index, round, candidate), so results do not depend on the world size.
+
+The round boundary.  With the HIP VAE on the pipeline (and `pipeline_args.device_handoff`, default true) a candidate is decoded
+ONCE per rank: the decoder's zero-halo output is kept for the round (`halos`), the PNG is written from its 8-bit levels
+(rf_image_levels; compression in one worker thread per rank, `PngWriter`), a verifier whose `score_batch` carries `wants_decoded`
+reads the same buffer, and a selected candidate becomes the next round's "cot" condition on the device: levels ->
+rf_pil_resize_to_vae_input (PIL's resize, bit for bit) -> one rf_vae_encode per parent and rank -> `Condition(moments=...)`, each child
+sampling the posterior with its own generator.  Files, scores and latents are those of the host path (`device_handoff: false`: decode
+in `_save`, in the verifier and in `candidate_condition`, PIL resize on the host, one VAE encode per child), bit for bit.
 """
 from __future__ import annotations
 
@@ -66,16 +74,55 @@ def build_pipeline(config: dict, device, synthetic: bool = False, small: bool = 
     return pipe
 
 
-def candidate_condition(pipe: FluxPipeline, latents: torch.Tensor, height: int, width: int, condition_size: int) -> Condition:
+def _has_hip_vae(pipe: FluxPipeline) -> bool:
+    from ..flux.vae_hip import HipVAE
+    return isinstance(pipe.vae, HipVAE) and pipe.image_processor is not None
+
+
+def _decode_input(pipe: FluxPipeline, latents: torch.Tensor, height: int, width: int) -> torch.Tensor:
+    z = pipe._unpack_latents(latents, height, width, pipe.vae_scale_factor)
+    return z / pipe.vae.config.scaling_factor + pipe.vae.config.shift_factor
+
+
+@torch.no_grad()
+def decode_halo(pipe: FluxPipeline, latents: torch.Tensor, height: int, width: int) -> torch.Tensor:
+    """One candidate's packed latents [1, S, 64] -> the HIP decoder's own output, zero-halo NHWC [(H + 2), (W + 2), C] bf16: what
+    `_save`, the CLIP verifier and `candidate_condition` all read, so a candidate needs ONE decode per rank."""
+    return pipe.vae.decode_halo(_decode_input(pipe, latents, height, width))[0]
+
+
+def _on_device_resize(pipe: FluxPipeline, condition_size: int) -> bool:
+    """The device path covers what the reference's hand-off does at a condition size the image processor leaves alone (a multiple of
+    its 16: `preprocess` would otherwise LANCZOS-resize the condition once more, on the host)."""
+    return _has_hip_vae(pipe) and condition_size % pipe.image_processor.vae_scale_factor == 0
+
+
+def levels_condition(pipe: FluxPipeline, levels: torch.Tensor, condition_size: int) -> Condition:
+    """uint8 levels [H, W, 3] on the device (a decoded candidate's, or an `--imgpath` PNG's) -> the "cot" Condition of the
+    reference's `resize((size, size))` + `Condition.encode`, with the VAE encoder run here, once, on the resized image."""
+    from ..flux import image_hip
+    _, xp = image_hip.resize_levels(levels, condition_size, condition_size, pipe.vae.image_pad)
+    return Condition("cot", moments=pipe.vae.encode_moments_halo(xp), position_delta=[0, -condition_size // 16])
+
+
+def candidate_condition(pipe: FluxPipeline, latents: torch.Tensor, height: int, width: int, condition_size: int,
+                        halo: Optional[torch.Tensor] = None, device: bool = True) -> Condition:
     """The condition a selected candidate becomes for the next round.  With a VAE on the pipeline this is the
     REFERENCE computation (tts_reflectionflow.py:273-279): decode the candidate (generate.py:302-307), take the 8-bit
     image the reference would have written to PNG and re-opened, `resize((condition_size, condition_size))` with PIL's
     default filter, and hand it over as `Condition(condition=img, "cot", position_delta=[0, -condition_size // 16])` --
     `Condition.encode` then runs `image_processor.preprocess` + `vae.encode(x).latent_dist.sample()` + shift/scale +
     pack (pipeline_tools.py:7-30).  Only the PNG file round trip itself is skipped (lossless).
-    Without a VAE (no weights offline) it falls back to `latent_to_condition`, a declared stand-in."""
+    Without a VAE (no weights offline) it falls back to `latent_to_condition`, a declared stand-in.
+    With the HIP VAE and `device` the same values are formed without leaving the device (`halo`: the candidate's decoded buffer if
+    the caller already has it; else it is decoded here, once): the image is never copied to the host and the encoder runs once for
+    all children.  `device=False` is the host path as written above."""
     if pipe.vae is None or pipe.image_processor is None:
         return latent_to_condition(latents, height, width, condition_size)
+    if device and _on_device_resize(pipe, condition_size):
+        from ..flux import image_hip
+        halo = decode_halo(pipe, latents, height, width) if halo is None else halo
+        return levels_condition(pipe, image_hip.levels_from_halo(halo), condition_size)
     z = pipe._unpack_latents(latents, height, width, pipe.vae_scale_factor)
     z = z / pipe.vae.config.scaling_factor + pipe.vae.config.shift_factor
     img = pipe.image_processor.postprocess(pipe.vae.decode(z.to(pipe.vae.dtype), return_dict=False)[0], output_type="pil")[0]
@@ -111,9 +158,57 @@ def latent_to_condition(latents: torch.Tensor, height: int, width: int, conditio
     return Condition("cot", tokens=tokens, ids=ids, position_delta=[0, -condition_size // 16])
 
 
-def _save(path: str, latents: torch.Tensor, pipe: FluxPipeline, height: int, width: int) -> str:
-    """Write one candidate: PNG like the reference when the pipeline has a VAE, else the packed latents as .pt.  Returns the file."""
+class PngWriter:
+    """PNG compression off the critical path: ONE worker thread per rank.  `submit` enqueues the device -> pinned-host copy of a
+    candidate's uint8 levels on the current stream and returns; the worker waits for that copy's event and writes the file.  `join`
+    returns when every submitted file is complete (before anything reads them: the round's artefact copies, the caller of a round)."""
+
+    def __init__(self):
+        from concurrent.futures import ThreadPoolExecutor
+        self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="rf-png")
+        self._pending = []
+
+    def submit(self, levels: torch.Tensor, file: str) -> None:
+        host = torch.empty(levels.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(levels, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self._pending.append(self._pool.submit(self._write, host, done, file))
+
+    @staticmethod
+    def _write(host: torch.Tensor, done, file: str) -> None:
+        from PIL import Image
+        done.synchronize()
+        Image.fromarray(host.numpy()).save(file)
+
+    def join(self) -> None:
+        pending, self._pending = self._pending, []
+        for f in pending:
+            f.result()                                                          # re-raises a failed write
+
+    def close(self) -> None:
+        try:
+            self.join()
+        finally:
+            self._pool.shutdown(wait=True)
+
+
+def _save(path: str, latents: torch.Tensor, pipe: FluxPipeline, height: int, width: int, halo: Optional[torch.Tensor] = None,
+          writer: Optional[PngWriter] = None, device: bool = True) -> str:
+    """Write one candidate: PNG like the reference when the pipeline has a VAE, else the packed latents as .pt.  Returns the file.
+    With the HIP VAE (and `device`) the PNG is written from rf_image_levels' uint8 output -- a 3 MB copy at 1024^2 instead of a
+    12 MB float one, the same pixels -- from `halo` if the caller has the decoded buffer, and by `writer`'s thread if one is given
+    (the file is then complete after `writer.join()`)."""
     os.makedirs(os.path.dirname(path), exist_ok=True)
+    if device and _has_hip_vae(pipe):
+        from ..flux import image_hip
+        levels = image_hip.levels_from_halo(decode_halo(pipe, latents, height, width) if halo is None else halo)
+        if writer is not None:
+            writer.submit(levels, path + ".png")
+        else:
+            from PIL import Image
+            Image.fromarray(levels.cpu().numpy()).save(path + ".png")
+        return path + ".png"
     if pipe.vae is not None and pipe.image_processor is not None:              # full pipeline available: PNG like the reference
         z = pipe._unpack_latents(latents, height, width, pipe.vae_scale_factor)
         z = z / pipe.vae.config.scaling_factor + pipe.vae.config.shift_factor
@@ -233,7 +328,9 @@ def run_reflection_search(config: dict, prompts: Optional[List[str]], output_dir
     `score_batch(latents [n, S, 64], seeds) -> (f32 [n], i32 [n])` scores generated candidates on the device (one call per
     round and rank); `score_images(paths, prompt) -> (f32, i32)` scores an `--imgpath` pool.  A `score_batch` that carries
     `wants_prompt = True` (tts/clip_verifier.py) is called as `score_batch(latents, seeds, prompt=<the ORIGINAL prompt>)`: the
-    reference scores every round against it (tts_reflectionflow.py:157-170, 345-352), not against the reflected prompts.
+    reference scores every round against it (tts_reflectionflow.py:157-170, 345-352), not against the reflected prompts.  One that
+    carries `wants_decoded = True` is, on the device hand-off path, also given `decoded=<this rank's decoded buffers, in row order>`
+    (HipVAE.decode_halo outputs) and does not decode again; any other callable keeps the two-argument contract.
 
     Deliberate deviations: the reference's `generate` call passes neither `latents`,
     `num_inference_steps` nor `guidance_scale` (so 28 steps / 3.5 / global-RNG noise apply and the `get_noises` seeds only
@@ -251,6 +348,9 @@ def run_reflection_search(config: dict, prompts: Optional[List[str]], output_dir
     if hasattr(pipe.vae, "check_geometry"):          # HIP VAE: refuse unsupported sizes before any candidate is generated
         pipe.vae.check_geometry(H, W, "candidate image")
         pipe.vae.check_geometry(csize, csize, "condition image")
+    # the round boundary on the device (module docstring); `"device_handoff": false` keeps the host path for an A/B comparison
+    handoff = bool(pa.get("device_handoff", True)) and _has_hip_vae(pipe)
+    writer = PngWriter() if handoff else None
     use_reflection = reflect is not None
     use_refine = refine is not None
     if use_reflection and not use_refine:
@@ -291,8 +391,9 @@ def run_reflection_search(config: dict, prompts: Optional[List[str]], output_dir
         updated_prompt = [prompt] * N                                           # :579
         reflections = [""] * N if use_reflection else None                      # :582-585
 
-        def generate_round(rnd, parents, parent_payload, round_prompts, subdir):
-            """This rank's candidates of one round -> (seeds, names, files, scores [(f, i)] of ALL candidates, local latents)."""
+        def generate_round(rnd, parents, parent_payload, parent_halos, round_prompts, subdir):
+            """This rank's candidates of one round -> (seeds, names, scores [(f, i)] of ALL candidates, local latents, local decoded
+            buffers).  `parent_halos`: the decoded buffers of the pool's candidates this rank generated (the device hand-off's cache)."""
             seeds = candidate_seeds(index + start_index, rnd, N)
             mine = list(shard.mine(N))
             uniq = list(dict.fromkeys(round_prompts[i] for i in mine))
@@ -301,6 +402,7 @@ def run_reflection_search(config: dict, prompts: Optional[List[str]], output_dir
             slot = {p: k for k, p in enumerate(uniq)}
             cond_cache: Dict[int, Condition] = {}                               # one decode -> resize per parent and rank
             local: Dict[int, torch.Tensor] = {}
+            halos: Dict[int, torch.Tensor] = {}
             for i in mine:
                 seed = seeds[i]
                 noise = get_noises(MAX_SEED, 1, H, W, device=dev, dtype=dtype, seeds=[seed])[seed]
@@ -310,7 +412,8 @@ def run_reflection_search(config: dict, prompts: Optional[List[str]], output_dir
                     if i < len(parents):
                         j = parents[i]
                         if j not in cond_cache:
-                            cond_cache[j] = _payload_condition(pipe, parent_payload[j], H, W, csize)
+                            cond_cache[j] = _payload_condition(pipe, parent_payload[j], H, W, csize, halo=parent_halos.get(j),
+                                                               device=handoff)
                         # Condition.encode samples the VAE posterior (pipeline_tools.py:10; the reference draws from the global
                         # RNG): a per-candidate generator makes the sample a function of the candidate's seed alone
                         conds = [cond_cache[j].with_generator(torch.Generator(device="cpu").manual_seed(seed))]
@@ -319,12 +422,19 @@ def run_reflection_search(config: dict, prompts: Optional[List[str]], output_dir
                                height=H, width=W, max_sequence_length=pe_all.shape[1],
                                num_inference_steps=pa["num_inference_steps"], guidance_scale=pa["guidance_scale"],
                                latents=noise, model_config=model_cfg, default_lora=True, output_type="latent").images
-                _save(os.path.join(outpath, subdir, f"{rnd}_round@{seed}"), lat, pipe, H, W)
+                if handoff:                                                     # THE decode of this candidate on this rank
+                    halos[i] = decode_halo(pipe, lat, H, W)
+                _save(os.path.join(outpath, subdir, f"{rnd}_round@{seed}"), lat, pipe, H, W, halo=halos.get(i), writer=writer, device=handoff)
                 local[i] = lat
-            scores = _score_local(shard, N, mine, local, seeds, verifier, bind_prompt(score_batch, prompt))
+            fn = bind_prompt(score_batch, prompt)
+            if handoff and mine and getattr(score_batch, "wants_decoded", False):
+                fn = functools.partial(fn, decoded=[halos[i] for i in mine])
+            scores = _score_local(shard, N, mine, local, seeds, verifier, fn)
+            if writer is not None:                                              # the files exist before anyone is told their names
+                writer.join()
             ext = ".png" if (pipe.vae is not None and pipe.image_processor is not None) else ".pt"
             names = [f"{subdir}/{rnd}_round@{s}{ext}" for s in seeds]
-            return seeds, names, scores, local
+            return seeds, names, scores, local, halos
 
         # ---- the pool
         if pools is not None:
@@ -335,10 +445,10 @@ def run_reflection_search(config: dict, prompts: Optional[List[str]], output_dir
             s_all, l_all = search.allgather_score_tensors(shard, len(pool_names), sc, lab)
             pool_scores = [(float(a), int(b)) for a, b in zip(s_all.tolist(), l_all.tolist())]
             pool_local: Dict[int, object] = {i: p for i, p in enumerate(pool_names)}      # files: every rank can read them
-            pool_on_disk = True
+            pool_on_disk, pool_halos = True, {}
             log.append({"prompt": prompt, "round": 0, "pool": pool_names, "scores": pool_scores})
         else:
-            seeds0, pool_names, pool_scores, pool_local = generate_round(0, None, None, [prompt] * N, "samples")
+            seeds0, pool_names, pool_scores, pool_local, pool_halos = generate_round(0, None, None, {}, [prompt] * N, "samples")
             pool_on_disk = False
             log.append({"prompt": prompt, "round": 0, "seeds": seeds0, "generated": pool_names, "scores": pool_scores})
 
@@ -381,7 +491,7 @@ def run_reflection_search(config: dict, prompts: Optional[List[str]], output_dir
                                      if new_reflections else list(refined))
                     round_prompts += [prompt] * (N - len(round_prompts))
             # ---- generation + scoring (:297-356)
-            seeds, names, scores, local = generate_round(rnd, sel, payload, round_prompts, "midimg")
+            seeds, names, scores, local, halos = generate_round(rnd, sel, payload, pool_halos, round_prompts, "midimg")
             parents = [selected_names[i] if i < len(sel) else None for i in range(N)]
             tree.record(rnd, names, scores, parents)                            # :358-395
             best_chain = tree.best_of_chains()
@@ -409,11 +519,14 @@ def run_reflection_search(config: dict, prompts: Optional[List[str]], output_dir
                 updated_prompt = refined                                        # :621-622
             log.append(rec)
             pool_names, pool_scores, pool_local, pool_on_disk = names, scores, local, False     # :623
+            pool_halos = halos                                                  # the old pool's decoded buffers are dropped here
         if shard.rank == 0:
             with open(os.path.join(outpath, "search_log.jsonl"), "w") as f:
                 for r in log:
                     f.write(json.dumps(r) + "\n")
         all_logs += log
+    if writer is not None:
+        writer.close()
     if shard.world_size > 1:
         torch.distributed.barrier()
     return all_logs
@@ -434,16 +547,23 @@ def _evaluation(name: str, score, scalar: bool) -> dict:
     return {"image_name": name, "label": "yes" if score[1] == 1 else "no", "score": score[0]}
 
 
-def _payload_condition(pipe: FluxPipeline, payload, height: int, width: int, condition_size: int) -> Condition:
+def _payload_condition(pipe: FluxPipeline, payload, height: int, width: int, condition_size: int, halo: Optional[torch.Tensor] = None,
+                       device: bool = True) -> Condition:
     """A parent -> its "cot" Condition (tts_reflectionflow.py:273-279): an image file is opened and resized as the reference
-    does; a candidate's packed latents go through `candidate_condition` (decode -> 8-bit image -> resize, or the latent stand-in)."""
+    does; a candidate's packed latents go through `candidate_condition` (decode -> 8-bit image -> resize, or the latent stand-in).
+    On the device path (`device`, HIP VAE) an RGB file uploads its uint8 levels and takes the same resize kernel as a candidate;
+    `halo` is the candidate's decoded buffer when this rank still holds it."""
     if isinstance(payload, str):
         if payload.endswith(".pt"):
-            return candidate_condition(pipe, torch.load(payload).to(pipe.device, pipe.dtype), height, width, condition_size)
+            return candidate_condition(pipe, torch.load(payload).to(pipe.device, pipe.dtype), height, width, condition_size, device=device)
         from PIL import Image
-        img = Image.open(payload).resize((condition_size, condition_size))
+        img = Image.open(payload)
+        if device and img.mode == "RGB" and _on_device_resize(pipe, condition_size):
+            import numpy as np
+            return levels_condition(pipe, torch.from_numpy(np.asarray(img).copy()).to(pipe.device), condition_size)
+        img = img.resize((condition_size, condition_size))
         return Condition(condition=img, condition_type="cot", position_delta=[0, -condition_size // 16])
-    return candidate_condition(pipe, payload, height, width, condition_size)
+    return candidate_condition(pipe, payload, height, width, condition_size, halo=halo, device=device)
 
 
 def _score_local(shard, n, mine, local, seeds, verifier, score_batch):
