@@ -252,6 +252,12 @@ int rf_quant_rows_fp8(const void* x0, int64_t ld0, int32_t K0, const void* x1, i
  *   x <- bf16( float(x) + dt * float(v) ),  dt = sigma_next - sigma */
 int rf_euler_step(void* x, const void* v, int64_t n, float dt, void* stream);
 
+/* Image-CFG combine (generate.py:250-272) + the Euler step above in one pass over [n] bf16:
+ *   d = bf16(pred - unc);  e = bf16(scale * d)  (fp32 product);  v = bf16(unc + e);  x <- bf16( float(x) + dt * float(v) )
+ * -- every rounding where the reference's three bf16 element-wise ops round, so the result is bit-equal to
+ * `unc + scale * (pred - unc)` followed by rf_euler_step.  NULL pointer: RF_ERR_NULL; x / pred / unc not 16-byte aligned: RF_ERR_ALIGN. */
+int rf_guided_euler_step(void* x, const void* pred, const void* unc, int64_t n, float scale, float dt, void* stream);
+
 /* out = bf16(silu(float(x)))  (the SiLU in front of every AdaLN linear) */
 int rf_silu(const void* x, void* out, int64_t n, void* stream);
 
@@ -376,6 +382,24 @@ int rf_flux_denoise(const rf_flux_dims* dims, const rf_flux_model* m,
                     const float* cos_tab, const float* sin_tab,
                     const float* dts, int32_t T, void* vel_scratch,
                     const rf_workspace* ws, void* stream);
+
+/* T-step denoise loop with image guidance (generate.py:250-276, `image_guidance_scale != 1`).  Per step, in this order on the
+ * one stream: rf_flux_forward with (cond_latents, mod_main_steps[i]) -> vel_scratch; rf_flux_forward with
+ * (unc_latents_steps[i], mod_unc_steps[i]) -> unc_scratch; rf_guided_euler_step.  Both forwards use `ws` one after the other
+ * (no stream is forked: a capture of this call is a linear graph); no allocation, no synchronisation.
+ *   unc_latents_steps: [T or 1][S_cond x in_ch] condition tokens of the unconditional pass, unc_stride elements apart
+ *                      (0 = the same tokens every step);
+ *   mod_unc_steps:     [T] table rows of the unconditional pass (guidance 1), mod_stride elements apart like mod_main_steps;
+ *   mod_cond:          the condition rows' table row, shared by both passes;
+ *   vel_scratch, unc_scratch: [S_img x in_ch] each.
+ * RF_ERR_NULL for a NULL pointer, RF_ERR_SHAPE for T <= 0 or dims->S_cond == 0 (guidance needs a condition). */
+int rf_flux_denoise_guided(const rf_flux_dims* dims, const rf_flux_model* m,
+                           void* latents, const void* cond_latents,
+                           const void* unc_latents_steps, int64_t unc_stride, const void* ctx,
+                           const void* mod_main_steps, const void* mod_unc_steps, int64_t mod_stride, const void* mod_cond,
+                           const float* cos_tab, const float* sin_tab,
+                           const float* dts, int32_t T, float scale, void* vel_scratch, void* unc_scratch,
+                           const rf_workspace* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * FLUX VAE (AutoencoderKL, 16 latent channels, 8x) -- SURVEY 8(f) row 1.  Replaces, either side of the denoise loop,

@@ -189,6 +189,7 @@ _SIGS = {
     "rf_attention": (C.c_int, [C.POINTER(rf_attn_desc), _P]),
     "rf_layernorm_modulate": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_float, _P]),
     "rf_euler_step": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P]),
+    "rf_guided_euler_step": (C.c_int, [_P, _P, _P, C.c_int64, C.c_float, C.c_float, _P]),
     "rf_silu": (C.c_int, [_P, _P, C.c_int64, _P]),
     "rf_add_inplace": (C.c_int, [_P, _P, C.c_int64, _P]),
     "rf_workspace_bytes": (C.c_int64, [C.POINTER(rf_flux_dims)]),
@@ -201,6 +202,9 @@ _SIGS = {
                                   C.POINTER(rf_workspace), _P]),
     "rf_flux_denoise": (C.c_int, [C.POINTER(rf_flux_dims), C.POINTER(rf_flux_model), _P, _P, _P, _P, C.c_int64, _P,
                                   _P, _P, C.POINTER(C.c_float), C.c_int32, _P, C.POINTER(rf_workspace), _P]),
+    "rf_flux_denoise_guided": (C.c_int, [C.POINTER(rf_flux_dims), C.POINTER(rf_flux_model), _P, _P, _P, C.c_int64, _P, _P, _P,
+                                         C.c_int64, _P, _P, _P, C.POINTER(C.c_float), C.c_int32, C.c_float, _P, _P,
+                                         C.POINTER(rf_workspace), _P]),
     "rf_vae_workspace_bytes": (C.c_int64, [C.POINTER(rf_vae_weights), C.c_int32, C.c_int32, C.c_int32]),
     "rf_vae_decode": (C.c_int, [C.POINTER(rf_vae_weights), _P, C.c_int32, C.c_int32, _P, C.POINTER(rf_workspace), _P]),
     "rf_vae_encode": (C.c_int, [C.POINTER(rf_vae_weights), _P, C.c_int32, C.c_int32, _P, C.POINTER(rf_workspace), _P]),

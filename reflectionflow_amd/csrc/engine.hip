@@ -576,3 +576,30 @@ extern "C" int rf_flux_denoise(const rf_flux_dims* dims, const rf_flux_model* m,
   }
   return RF_OK;
 }
+
+// Image-guided loop (generate.py:250-276): per step the conditional forward, the unconditional forward (its own condition
+// tokens and its own table row: guidance = 1) and the guided Euler step.  The two forwards share the workspace, so they run
+// one after the other on the one stream: a linear chain of launches, nothing forked.
+extern "C" int rf_flux_denoise_guided(const rf_flux_dims* dims, const rf_flux_model* m, void* latents,
+                                      const void* cond_latents, const void* unc_latents_steps, int64_t unc_stride,
+                                      const void* ctx, const void* mod_main_steps, const void* mod_unc_steps,
+                                      int64_t mod_stride, const void* mod_cond, const float* cos_tab, const float* sin_tab,
+                                      const float* dts, int32_t T, float scale, void* vel_scratch, void* unc_scratch,
+                                      const rf_workspace* ws, void* stream) {
+  RF_REQUIRE(dts && vel_scratch && unc_scratch && latents && mod_main_steps && mod_unc_steps && m && dims, RF_ERR_NULL,
+             "rf_flux_denoise_guided: NULL pointer");
+  RF_REQUIRE(T > 0, RF_ERR_SHAPE, "rf_flux_denoise_guided: T=%d", T);
+  RF_REQUIRE(dims->S_cond > 0, RF_ERR_SHAPE, "rf_flux_denoise_guided: S_cond=%d (image guidance needs a condition)", dims->S_cond);
+  RF_REQUIRE(cond_latents && unc_latents_steps && mod_cond, RF_ERR_NULL, "rf_flux_denoise_guided: condition inputs NULL");
+  RF_REQUIRE(unc_stride >= 0 && mod_stride >= 0, RF_ERR_SHAPE, "rf_flux_denoise_guided: negative stride");
+  const int64_t n = (int64_t)dims->S_img * m->in_ch;
+  for (int i = 0; i < T; ++i) {
+    const bf16_t* mod = (const bf16_t*)mod_main_steps + (int64_t)i * mod_stride;
+    const bf16_t* mod_u = (const bf16_t*)mod_unc_steps + (int64_t)i * mod_stride;
+    const bf16_t* unc = (const bf16_t*)unc_latents_steps + (int64_t)i * unc_stride;
+    RF_TRY(rf_flux_forward(dims, m, latents, cond_latents, ctx, mod, mod_cond, cos_tab, sin_tab, vel_scratch, ws, stream));
+    RF_TRY(rf_flux_forward(dims, m, latents, unc, ctx, mod_u, mod_cond, cos_tab, sin_tab, unc_scratch, ws, stream));
+    RF_TRY(rf_guided_euler_step(latents, vel_scratch, unc_scratch, n, scale, dts[i], stream));
+  }
+  return RF_OK;
+}

@@ -2,7 +2,7 @@
 // row (or per 4 head-rows), fp32 math, a single bf16 rounding on the way out.
 //   rf_layernorm_modulate : LayerNorm(no affine) + (1+scale)*x + shift   (AdaLN-Zero family)
 //   rf_qk_rmsnorm_rope    : per-head RMSNorm(q,k) + interleaved-pair RoPE, in place
-//   rf_euler_step / rf_silu / rf_add_inplace : element-wise
+//   rf_euler_step / rf_guided_euler_step / rf_silu / rf_add_inplace : element-wise
 #include "common.hpp"
 
 namespace rf {
@@ -231,6 +231,33 @@ __global__ __launch_bounds__(256) void euler_kernel(bf16_t* __restrict__ x, cons
   }
 }
 
+// Image-CFG combine + Euler step in one pass (generate.py:250-276): n = unc + s*(pred - unc), x <- x + dt*n.  The per-step
+// path forms n with three bf16 torch element-wise ops, so every intermediate is rounded to bf16 exactly where torch rounds
+// it (difference, fp32 product with the fp32 scalar, sum); the Euler update of n is euler_kernel's expression verbatim.
+__device__ __forceinline__ float guided_velocity(float pred, float unc, float s) {
+  const float d = bf2f(f2bf(pred - unc));
+  const float e = bf2f(f2bf(s * d));
+  return bf2f(f2bf(unc + e));
+}
+
+__global__ __launch_bounds__(256) void guided_euler_kernel(bf16_t* __restrict__ x, const bf16_t* __restrict__ pred,
+                                                           const bf16_t* __restrict__ unc, int64_t n, float s, float dt) {
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
+  if (i + 8 <= n) {
+    float a[8], p[8], u[8], b[8];
+    unpack8(*(const u32x4*)(x + i), a);
+    unpack8(*(const u32x4*)(pred + i), p);
+    unpack8(*(const u32x4*)(unc + i), u);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b[j] = guided_velocity(p[j], u[j], s);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a[j] = a[j] + dt * b[j];
+    *(u32x4*)(x + i) = pack8(a);
+  } else {
+    for (int64_t j = i; j < n; ++j) x[j] = f2bf(bf2f(x[j]) + dt * guided_velocity(bf2f(pred[j]), bf2f(unc[j]), s));
+  }
+}
+
 __global__ __launch_bounds__(256) void silu_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ out, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) {
@@ -444,6 +471,20 @@ extern "C" int rf_euler_step(void* x, const void* v, int64_t n, float dt, void* 
   ProfScope prof(RF_KC_ROWOP, 6.0 * (double)n, (hipStream_t)stream);
   hipLaunchKernelGGL(euler_kernel, dim3((unsigned)((n + 2047) / 2048)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x,
                      (const bf16_t*)v, n, dt);
+  RF_LAUNCH_CHECK();
+  return RF_OK;
+}
+
+extern "C" int rf_guided_euler_step(void* x, const void* pred, const void* unc, int64_t n, float scale, float dt,
+                                    void* stream) {
+  using namespace rf;
+  if (n <= 0) return RF_OK;
+  RF_REQUIRE(x && pred && unc, RF_ERR_NULL, "rf_guided_euler_step: NULL pointer");
+  RF_REQUIRE(aligned16(x) && aligned16(pred) && aligned16(unc), RF_ERR_ALIGN,
+             "rf_guided_euler_step: operands must be 16-byte aligned");
+  ProfScope prof(RF_KC_ROWOP, 8.0 * (double)n, (hipStream_t)stream);
+  hipLaunchKernelGGL(guided_euler_kernel, dim3((unsigned)((n + 2047) / 2048)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x,
+                     (const bf16_t*)pred, (const bf16_t*)unc, n, scale, dt);
   RF_LAUNCH_CHECK();
   return RF_OK;
 }

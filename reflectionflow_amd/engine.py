@@ -448,26 +448,81 @@ class FluxEngine:
         T = len(dts)
         if mod_steps.shape != (T, self.mod_cols) or not mod_steps.is_contiguous():
             raise ops.RFError("FluxEngine.denoise: mod_steps must be contiguous [T, mod_cols]")
+        use_graph = self._graph_rule(use_graph, T)
+        arr = (C.c_float * T)(*[float(x) for x in dts])
+
+        def launch(b, scr):
+            L.check(self.lib.rf_flux_denoise(
+                C.byref(d), C.byref(self.model), b["lat"].data_ptr(), ops.ptr(b["cond"]), b["ctx"].data_ptr(),
+                b["mod"].data_ptr(), b["mod"].stride(0), ops.ptr(b["mc"]), b["cos"].data_ptr(), b["sin"].data_ptr(),
+                arr, T, scr[0].data_ptr(), C.byref(ws), ops.stream_ptr()), "rf_flux_denoise")
+
+        key = (bytes(d), T, tuple(float(x) for x in dts), ws.base, tuple(cos.shape))
+        bufs = dict(lat=latents, ctx=ctx, mod=mod_steps, cos=cos, sin=sin, cond=cond_latents, mc=mod_cond)
+        return self._run_loop(key, bufs, 1, launch, use_graph)
+
+    def denoise_guided(self, latents, ctx, mod_steps, mod_unc_steps, dts, cos, sin, cond_latents, unc_latents, mod_cond, scale,
+                       model_config=None, c_factor=None, use_graph: Optional[bool] = None) -> torch.Tensor:
+        """The T-step loop with image guidance (generate.py:250-276) in ONE C call, rf_flux_denoise_guided: per step the conditional
+        forward, the unconditional forward (unc_latents [T or 1, S_cond, in_ch]: its condition tokens per step, one set = the same
+        every step; mod_unc_steps [T, mod_cols]: its table rows, guidance 1) and the guided Euler step; latents [S_img, in_ch] updated
+        in place.  Graph rule and cache as denoise(): a linear graph of T x 2 forwards, keyed additionally by the scale (a kernel
+        argument baked into the capture) and the shape of unc_latents."""
+        if cond_latents is None or mod_cond is None or unc_latents is None:
+            raise ops.RFError("FluxEngine.denoise_guided: image guidance needs a condition (cond_latents, unc_latents, mod_cond)")
+        d = self.dims(ctx.shape[0], latents.shape[0], cond_latents.shape[0], model_config, c_factor)
+        ws = self.workspace(d)
+        T = len(dts)
+        for t, what in ((mod_steps, "mod_steps"), (mod_unc_steps, "mod_unc_steps")):
+            if t.shape != (T, self.mod_cols) or not t.is_contiguous():
+                raise ops.RFError(f"FluxEngine.denoise_guided: {what} must be contiguous [T, mod_cols]")
+        if unc_latents.dim() != 3 or unc_latents.shape[0] not in (1, T) or unc_latents.shape[1:] != cond_latents.shape:
+            raise ops.RFError("FluxEngine.denoise_guided: unc_latents must be [T or 1, S_cond, in_ch]")
+        for t in (latents, ctx, cond_latents, unc_latents, mod_steps, mod_unc_steps, mod_cond):
+            if not (t.is_contiguous() and t.dtype == torch.bfloat16 and t.is_cuda):
+                raise ops.RFError("FluxEngine.denoise_guided: inputs must be contiguous bf16 device tensors")
+        if cos.shape[0] != d.S_txt + d.S_img + d.S_cond:
+            raise ops.RFError("FluxEngine.denoise_guided: rope tables do not cover [txt|img|cond]")
+        use_graph = self._graph_rule(use_graph, T)
+        arr = (C.c_float * T)(*[float(x) for x in dts])
+        unc_stride = 0 if unc_latents.shape[0] == 1 else unc_latents.stride(0)
+
+        def launch(b, scr):
+            L.check(self.lib.rf_flux_denoise_guided(
+                C.byref(d), C.byref(self.model), b["lat"].data_ptr(), b["cond"].data_ptr(), b["unc"].data_ptr(), unc_stride,
+                b["ctx"].data_ptr(), b["mod"].data_ptr(), b["modu"].data_ptr(), b["mod"].stride(0), b["mc"].data_ptr(),
+                b["cos"].data_ptr(), b["sin"].data_ptr(), arr, T, float(scale), scr[0].data_ptr(), scr[1].data_ptr(),
+                C.byref(ws), ops.stream_ptr()), "rf_flux_denoise_guided")
+
+        key = (bytes(d), T, tuple(float(x) for x in dts), ws.base, tuple(cos.shape), "guided", float(scale), unc_latents.shape[0])
+        bufs = dict(lat=latents, ctx=ctx, mod=mod_steps, modu=mod_unc_steps, cos=cos, sin=sin, cond=cond_latents, unc=unc_latents,
+                    mc=mod_cond)
+        return self._run_loop(key, bufs, 2, launch, use_graph)
+
+    @staticmethod
+    def _graph_rule(use_graph: Optional[bool], T: int) -> bool:
         if use_graph is None:
             env = os.environ.get("RF_DENOISE_GRAPH", "")
             use_graph = (env not in ("", "0")) if env != "" else T >= 16
         if ops.profile.open_count > 0:
             use_graph = False                                # the hook records one event per launch: needs the eager launches
-        arr = (C.c_float * T)(*[float(x) for x in dts])
+        return use_graph
 
-        def launch(lat, cx, mod, cs, sn, cond, mc, vel):
-            L.check(self.lib.rf_flux_denoise(
-                C.byref(d), C.byref(self.model), lat.data_ptr(), ops.ptr(cond), cx.data_ptr(),
-                mod.data_ptr(), mod.stride(0), ops.ptr(mc), cs.data_ptr(), sn.data_ptr(),
-                arr, T, vel.data_ptr(), C.byref(ws), ops.stream_ptr()), "rf_flux_denoise")
+    def _run_loop(self, key, bufs, n_scratch, launch, use_graph) -> torch.Tensor:
+        """Shared by denoise() / denoise_guided(): `launch(bufs, scratch)` enqueues one whole loop on the current stream reading the
+        tensors of `bufs` (name -> tensor or None; bufs["lat"] is updated in place) and n_scratch latents-sized scratch buffers --
+        either directly, or captured once per `key` over static copies of `bufs` and replayed."""
+        latents = bufs["lat"]
+
+        def eager():
+            launch(bufs, [torch.empty_like(latents) for _ in range(n_scratch)])
 
         if not use_graph or not self._eager_done:
             # (the first launch of a process runs eagerly even under use_graph: one-time hipFuncSetAttribute / device queries of
             #  the library must not happen inside a stream capture)
-            launch(latents, ctx, mod_steps, cos, sin, cond_latents, mod_cond, torch.empty_like(latents))
+            eager()
             self._eager_done = True
             return latents
-        key = (bytes(d), T, tuple(float(x) for x in dts), ws.base, tuple(cos.shape))
         ent = self._graphs.pop(key, None)                    # LRU: a hit moves to the most-recently-used end (re-inserted below)
         if ent is None:
             # a workload that cycles through more keys than the cache holds would re-capture T x ~300 nodes per call (a capture also
@@ -477,29 +532,29 @@ class FluxEngine:
             n_cap, n_eager = self._graph_captures.pop(key, (0, 0))
             if n_cap >= 2 and n_eager < 8:
                 self._graph_captures[key] = (n_cap, n_eager + 1)
-                launch(latents, ctx, mod_steps, cos, sin, cond_latents, mod_cond, torch.empty_like(latents))
+                eager()
                 return latents
             self._graph_captures[key] = (1 if n_cap >= 2 else n_cap + 1, 0)
             while len(self._graph_captures) > 64:
                 self._graph_captures.pop(next(iter(self._graph_captures)))
-            if len(self._graphs) >= self._graph_cache_max:   # a captured 50-step loop holds ~110 MB of static tables
+            # a captured 50-step loop holds ~110 MB of static tables at FLUX.1-dev size (T rows of 2.1 MB); a guided one twice that
+            # (mod_unc_steps is a second [T, mod_cols] table) plus its T sets of condition tokens (6.5 MB for a 512^2 condition)
+            if len(self._graphs) >= self._graph_cache_max:
                 self._graphs.pop(next(iter(self._graphs)))
-            st = dict(lat=torch.empty_like(latents), ctx=torch.empty_like(ctx), mod=torch.empty_like(mod_steps), cos=torch.empty_like(cos),
-                      sin=torch.empty_like(sin), vel=torch.empty_like(latents),
-                      cond=None if cond_latents is None else torch.empty_like(cond_latents),
-                      mc=None if mod_cond is None else torch.empty_like(mod_cond))
+            st = {k_: None if v is None else torch.empty_like(v) for k_, v in bufs.items()}
+            scr = [torch.empty_like(latents) for _ in range(n_scratch)]
             graph = torch.cuda.CUDAGraph()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.graph(graph, stream=side):
-                launch(st["lat"], st["ctx"], st["mod"], st["cos"], st["sin"], st["cond"], st["mc"], st["vel"])
+                launch(st, scr)
             torch.cuda.current_stream().wait_stream(side)
-            ent = (graph, st)
+            ent = (graph, st, scr)
         else:
             self._graph_captures.pop(key, None)              # replayed from the cache: it fits, forget its capture history
         self._graphs[key] = ent
-        graph, st = ent
-        for k_, src in (("lat", latents), ("ctx", ctx), ("mod", mod_steps), ("cos", cos), ("sin", sin), ("cond", cond_latents), ("mc", mod_cond)):
+        graph, st, _ = ent
+        for k_, src in bufs.items():
             if src is not None:
                 st[k_].copy_(src)
         graph.replay()

@@ -3,11 +3,14 @@ Same name, keyword surface (`prepare_params`) and return object as the reference
 train_flux/flux/generate.py:74-321.
 
 The T-step loop (reference :216-296) has two forms here:
-  * the FAST path -- no per-step callback, image_guidance_scale == 1 (what the tts scripts use):
-    the modulation tables of all T timesteps are computed up front, then ONE C call
-    (rf_flux_denoise) runs T x (forward + Euler) back to back on the stream;
+  * the FAST path -- no per-step callback (what the tts scripts use): the modulation tables of all
+    T timesteps are computed up front, then ONE C call (rf_flux_denoise) runs T x (forward + Euler)
+    back to back on the stream.  With image_guidance_scale != 1 (the FLUX-Corrector sampling call,
+    :250-272) the unconditional pass's tables and condition tokens are prepared up front as well
+    and ONE rf_flux_denoise_guided call runs T x (forward, forward, guided Euler);
   * the GENERAL path -- per step `tranformer_forward` + `scheduler.step`, supporting
-    callback_on_step_end and the image-CFG second pass (:250-272), quirks included.
+    callback_on_step_end, joint_attention_kwargs, and the image-CFG second pass (:250-272, quirks
+    included) for the cases the guided fast path does not take (batch > 1, no guidance embedder).
 Text encoding, condition VAE-encode and VAE decode stay PyTorch modules on the pipeline object.
 """
 from __future__ import annotations
@@ -124,11 +127,19 @@ def generate(pipeline, conditions: List[Condition] = None, config_path: str = No
     timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, timesteps,
                                                         sigmas, mu=mu)
 
-    fast = callback_on_step_end is None and image_guidance_scale == 1.0 and joint_attention_kwargs is None
+    fast = callback_on_step_end is None and joint_attention_kwargs is None
+    if image_guidance_scale != 1.0:
+        # the guided loop on the device needs what the per-step second pass needs (a condition to re-encode, a guidance
+        # embedder for `ones_like(guidance)`) and is one sample wide; every other case keeps the per-step path below
+        fast = fast and condition is not None and bool(self.transformer.config.guidance_embeds) and latents.shape[0] == 1
     if fast:
+        unc_tokens = None
+        if image_guidance_scale != 1.0:
+            unc_tokens = _unconditional_tokens(self, condition, num_inference_steps).to(latents)
         latents = _denoise_fast(self, latents, prompt_embeds, pooled_prompt_embeds, text_ids, latent_image_ids,
                                 timesteps, guidance_scale, condition_latents if use_condition else None,
-                                condition_ids if use_condition else None, model_config)
+                                condition_ids if use_condition else None, model_config,
+                                image_guidance_scale=image_guidance_scale, unc_tokens=unc_tokens)
     else:
         with self.progress_bar(total=num_inference_steps) as progress_bar:
             for i, t in enumerate(timesteps):
@@ -183,9 +194,27 @@ def generate(pipeline, conditions: List[Condition] = None, config_path: str = No
     return FluxPipelineOutput(images=image)
 
 
+def _unconditional_tokens(pipe, condition, T):
+    """The condition tokens of the T unconditional passes, [T or 1, S_cond, in_ch]: what T x `condition.encode(pipe, empty=True)`
+    (reference :252; `empty=True` still encodes the real condition, condition.py:114-121) return, drawn in the same order from the
+    same generator / global RNG.  Pre-encoded tokens are one set; moments are T posterior samples; an image is encoded ONCE (the
+    encoder is deterministic, only the posterior sample differs from step to step) and sampled T times from its moments."""
+    from .pipeline_tools import tokens_from_posterior
+    if condition.tokens is not None:
+        return condition.tokens[:1]
+    if condition.moments is not None:
+        from .vae import DiagonalGaussianDistribution
+        dist = DiagonalGaussianDistribution(condition.moments[None])
+    else:
+        images = pipe.image_processor.preprocess(condition.condition)
+        dist = pipe.vae.encode(images.to(pipe.device).to(pipe.dtype)).latent_dist
+    return torch.cat([tokens_from_posterior(pipe, dist, condition.generator)[0][:1] for _ in range(T)], 0)
+
+
 def _denoise_fast(pipe, latents, prompt_embeds, pooled, text_ids, img_ids, timesteps, guidance_scale,
-                  condition_latents, condition_ids, model_config):
-    """All-steps modulation tables up front, then one rf_flux_denoise call per sample."""
+                  condition_latents, condition_ids, model_config, image_guidance_scale=1.0, unc_tokens=None):
+    """All-steps modulation tables up front, then one rf_flux_denoise call per sample -- or, with image guidance
+    (unc_tokens [T or 1, S_cond, in_ch], batch 1), one rf_flux_denoise_guided call."""
     tr = pipe.transformer
     eng = E.engine_for(tr)
     dtype = tr.dtype
@@ -213,6 +242,15 @@ def _denoise_fast(pipe, latents, prompt_embeds, pooled, text_ids, img_ids, times
             c_ts = torch.zeros(1, device=dev, dtype=dtype)                          # c_t = 0
             c_g = torch.ones(1, device=dev, dtype=dtype) * 1000 if tr.config.guidance_embeds else None
             mod_cond = eng.mod_table(eng.temb(c_ts, c_g, pooled[b:b + 1].to(dtype)), lora=True)[0]
+        if unc_tokens is not None:
+            # the second pass of :253-255: same timestep, guidance = ones_like(guidance) (fp32 ones -> dtype, x1000 in the
+            # transformer), the same cond_temb -- so only the main table differs between the two forwards of a step
+            g1 = torch.ones(T, device=dev).to(dtype) * 1000
+            mod_unc = eng.mod_table(eng.temb(ts, g1, p), lora=latent_lora)
+            eng.denoise_guided(out[b], prompt_embeds[b].to(dtype).contiguous(), mod_steps, mod_unc, dts, cos, sin,
+                               condition_latents[b].to(dtype).contiguous(), unc_tokens.to(dtype).contiguous(), mod_cond,
+                               float(image_guidance_scale), model_config=model_config, c_factor=cf)
+            continue
         eng.denoise(out[b], prompt_embeds[b].to(dtype).contiguous(), mod_steps, dts, cos, sin,
                     cond_latents=condition_latents[b].to(dtype).contiguous() if use_condition else None,
                     mod_cond=mod_cond, model_config=model_config, c_factor=cf)

@@ -18,7 +18,7 @@ from . import _lib as L
 from ._lib import (RF_EPI_GATE_RES, RF_EPI_GELU, RF_EPI_QKV, RF_EPI_QKV_GELU, RF_EPI_STORE, RFError)
 
 __all__ = ["linear", "gemm", "build_gemm_desc", "time_gemm", "Group", "Seg", "qk_rmsnorm_rope", "attention", "layernorm_modulate",
-           "euler_step_", "silu", "add_", "alloc_attn_operands", "stream_ptr", "ptr", "RFError", "QK_PRESCALE", "profile",
+           "euler_step_", "guided_euler_step_", "silu", "add_", "alloc_attn_operands", "stream_ptr", "ptr", "RFError", "QK_PRESCALE", "profile",
            "quantize_weight_fp8", "dequantize_fp8", "quant_rows_fp8", "layernorm_modulate_fp8", "gemm_w8a8", "qk_score_bound",
            "gemm_schedule", "attn_kernel"]
 
@@ -385,6 +385,18 @@ def euler_step_(x: torch.Tensor, v: torch.Tensor, dt: float):
     if not (x.is_contiguous() and v.is_contiguous()) or x.numel() != v.numel():
         raise RFError("euler_step_: x and v must be contiguous and equally sized")
     L.check(lib.rf_euler_step(x.data_ptr(), v.data_ptr(), x.numel(), float(dt), stream_ptr()), "rf_euler_step")
+    return x
+
+
+def guided_euler_step_(x: torch.Tensor, pred: torch.Tensor, unc: torch.Tensor, scale: float, dt: float):
+    """x <- x + dt * bf16(unc + bf16(scale * bf16(pred - unc))): the image-CFG combine and the Euler step in one pass, rounded
+    where `unc + scale * (pred - unc)` on bf16 tensors rounds."""
+    lib = L.load()
+    _chk(x, "x"), _chk(pred, "pred"), _chk(unc, "unc")
+    if not (x.is_contiguous() and pred.is_contiguous() and unc.is_contiguous()) or not (x.numel() == pred.numel() == unc.numel()):
+        raise RFError("guided_euler_step_: x, pred and unc must be contiguous and equally sized")
+    L.check(lib.rf_guided_euler_step(x.data_ptr(), pred.data_ptr(), unc.data_ptr(), x.numel(), float(scale), float(dt), stream_ptr()),
+            "rf_guided_euler_step")
     return x
 
 
