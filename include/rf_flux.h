@@ -547,6 +547,25 @@ int rf_clip_preprocess(const void* img, int64_t s_img, int64_t s_row, int64_t s_
 int64_t rf_clip_vision_workspace_bytes(const rf_clip_vision_weights* w, int32_t B);
 /* patches [B * (image_size / patch)^2][K_pad] (rf_clip_preprocess) -> image_embeds [B][proj_dim] bf16; 1 <= B <= 64 */
 int rf_clip_vision_encode(const rf_clip_vision_weights* w, const void* patches, int32_t B, void* image_embeds, const rf_workspace* ws, void* stream);
+
+/* ViT-H/14 towers (PickScore, HPSv2, LAION CLIP-H: the same CLIPModel, vision hidden 1280 = 16 heads x 80, hidden_act "gelu").
+ * Additive to ABI v17: no struct above changes, the four entry points above ARE the calls below with {64, RF_CLIP_ACT_QUICK_GELU}.
+ *   head_dim  64 | 80; hidden == heads * head_dim.  The binding folds 1/sqrt(head_dim) into q_proj (weights and bias).
+ *   act       the MLP's activation: quick_gelu, or gelu = x/2 (1 + erf(x / sqrt 2)) in fp32, rounded to bf16 once (F.gelu on bf16).
+ * A head's K and V^T stay resident in the LDS: S_pad <= 512 keys at head dim 64, <= 480 at head dim 80 (257 tokens of a 224-px
+ * ViT-H/14 need 288); more returns RF_ERR_SHAPE from the size query and the encode call alike.  A hidden width that is no multiple
+ * of the GEMM's 64-element K-tile (test-size towers; 1280 is one): every weight whose K axis is `hidden` (w_qk, w_v, w_o, w_fc1,
+ * proj) is passed with row pitch round_up(hidden, 64), zero beyond `hidden`.  Other head dims / activations: RF_ERR_UNSUPPORTED. */
+enum { RF_CLIP_ACT_QUICK_GELU = 0, RF_CLIP_ACT_GELU = 1 };
+typedef struct rf_clip_tower_opts { int32_t head_dim; int32_t act; } rf_clip_tower_opts;
+int64_t rf_clip_text_workspace_bytes_opts(const rf_clip_weights* w, const rf_clip_tower_opts* o, int32_t B, int32_t S);
+int rf_clip_text_encode_opts(const rf_clip_weights* w, const rf_clip_tower_opts* o, const int32_t* ids, int32_t B, int32_t S, const int32_t* eos_pos,
+                             void* last_hidden, void* pooled, const rf_workspace* ws, void* stream);
+int64_t rf_clip_vision_workspace_bytes_opts(const rf_clip_vision_weights* w, const rf_clip_tower_opts* o, int32_t B);
+int rf_clip_vision_encode_opts(const rf_clip_vision_weights* w, const rf_clip_tower_opts* o, const void* patches, int32_t B, void* image_embeds,
+                               const rf_workspace* ws, void* stream);
+/* x[0 .. n) bf16 in place <- gelu (the RF_CLIP_ACT_GELU row kernel on its own); n % 8 == 0, x 16-byte aligned */
+int rf_gelu_erf_inplace(void* x, int64_t n, void* stream);
 /* scores[b] = exp(logit_scale) * <img_b / |img_b|, txt / |txt|> in fp32 (img [B][P], txt [P] bf16; logit_scale = the model's
  * log-domain parameter); one workgroup per row, fixed reduction order */
 int rf_clip_score(const void* img, const void* txt, float logit_scale, float* scores, int32_t B, int32_t P, void* stream);

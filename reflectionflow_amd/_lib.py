@@ -170,6 +170,14 @@ class rf_clip_vision_weights(C.Structure):
                                           "proj", "mask")] + [("layer", C.POINTER(rf_clip_layer))]
 
 
+class rf_clip_tower_opts(C.Structure):
+    _fields_ = [("head_dim", C.c_int32), ("act", C.c_int32)]
+
+
+RF_CLIP_ACT_QUICK_GELU, RF_CLIP_ACT_GELU = 0, 1
+CLIP_ACTS = {"quick_gelu": RF_CLIP_ACT_QUICK_GELU, "gelu": RF_CLIP_ACT_GELU}
+
+
 # every symbol include/rf_flux.h (the product ABI) declares: (restype, argtypes)
 _SIGS = {
     "rf_last_error": (C.c_char_p, []),
@@ -218,6 +226,14 @@ _SIGS = {
     "rf_clip_vision_workspace_bytes": (C.c_int64, [C.POINTER(rf_clip_vision_weights), C.c_int32]),
     "rf_clip_vision_encode": (C.c_int, [C.POINTER(rf_clip_vision_weights), _P, C.c_int32, _P, C.POINTER(rf_workspace), _P]),
     "rf_clip_score": (C.c_int, [_P, _P, C.c_float, _P, C.c_int32, C.c_int32, _P]),
+    # ViT-H/14 towers: head dim and activation per call (additive to v17; the four entry points above = these with {64, quick_gelu})
+    "rf_clip_text_workspace_bytes_opts": (C.c_int64, [C.POINTER(rf_clip_weights), C.POINTER(rf_clip_tower_opts), C.c_int32, C.c_int32]),
+    "rf_clip_text_encode_opts": (C.c_int, [C.POINTER(rf_clip_weights), C.POINTER(rf_clip_tower_opts), _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                           _P, _P, C.POINTER(rf_workspace), _P]),
+    "rf_clip_vision_workspace_bytes_opts": (C.c_int64, [C.POINTER(rf_clip_vision_weights), C.POINTER(rf_clip_tower_opts), C.c_int32]),
+    "rf_clip_vision_encode_opts": (C.c_int, [C.POINTER(rf_clip_vision_weights), C.POINTER(rf_clip_tower_opts), _P, C.c_int32, _P,
+                                             C.POINTER(rf_workspace), _P]),
+    "rf_gelu_erf_inplace": (C.c_int, [_P, C.c_int64, _P]),
     # round hand-off of the reflection search (csrc/image_handoff.hip)
     "rf_image_levels": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rf_pil_resize_to_vae_input": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32,

@@ -3,7 +3,8 @@
 // original prompt.  New here: the image preprocessing (8-bit levels -> CLIPImageProcessor's resize / crop / normalise -> im2col patch
 // rows), the token assembly row kernel and the fused normalise-and-dot score.  The encoder layers are the text tower's
 // (text.hip clip_layers: bf16 MFMA GEMM, attn64_kernel, rf_layernorm_modulate); the attention masks the padded keys (T = 257 tokens
-// of ViT-L/14 at 224 live in S_pad = 288 rows).
+// of ViT-L/14 at 224 live in S_pad = 288 rows).  rf_clip_tower_opts picks the head dim (64 | 80: attn64_kernel / attn80_kernel) and the
+// activation (quick_gelu | gelu) per call: ViT-H/14 (PickScore, HPSv2, LAION CLIP-H) is hidden 1280 = 16 heads x 80 with erf GELU.
 //
 // Batch invariance.  The search orders candidates by these scores and a rank scores its own candidates in one call, so a row's value
 // must not depend on how many images share the call (tts/search.py: score_batch implementations are row-wise batch-invariant).
@@ -11,7 +12,7 @@
 //     256x256 tile per workgroup that walks the WHOLE K range in order (sk_mode() is 0 for TILE256, the split-K branch is 128-tile
 //     only), so an output element's K order is fixed whatever M is.  AUTO (the text towers' policy) picks 128 / 256 tiles, split-K
 //     or stream-K from M -- i.e. from the batch size;
-//   * attn64_kernel's QI variant (picked from heads * B) only regroups query tiles into workgroups: each query row's scores, softmax
+//   * attn64_kernel's / attn80_kernel's QI variant (picked from heads * B) only regroups query tiles into workgroups: each query row's scores, softmax
 //     and PV sums run in the same order in both;
 //   * LayerNorm, token assembly, preprocessing and the score are one row / image per thread group.
 #include "text_internal.hpp"
@@ -189,36 +190,47 @@ extern "C" int rf_clip_preprocess(const void* img, int64_t s_img, int64_t s_row,
   return RF_OK;
 }
 
-static int vision_check(const rf_clip_vision_weights* w, const char* who) {
+static int vision_check(const rf_clip_vision_weights* w, const rf_clip_tower_opts* o, const char* who) {
   RF_REQUIRE(w && w->layer && w->patch_w && w->class_embed && w->pos_embed && w->pre_ln_scale && w->pre_ln_shift && w->post_ln_scale &&
                  w->post_ln_shift && w->proj && w->mask, RF_ERR_NULL, "%s: weights NULL", who);
-  RF_REQUIRE(w->layers > 0 && w->heads > 0 && w->hidden == w->heads * 64 && w->hidden <= 4096 && w->inter > 0 && w->inter % 64 == 0 && w->proj_dim > 0 &&
-                 w->proj_dim % 8 == 0, RF_ERR_SHAPE, "%s: layers=%d heads=%d hidden=%d inter=%d proj_dim=%d (need hidden = 64 * heads <= 4096, inter %% 64 "
-             "== 0, proj_dim %% 8 == 0)", who, w->layers, w->heads, w->hidden, w->inter, w->proj_dim);
+  RF_REQUIRE(w->layers > 0 && w->heads > 0 && w->hidden > 0 && w->hidden % 8 == 0 && w->hidden <= 4096 && w->inter > 0 && w->inter % 64 == 0 &&
+                 w->proj_dim > 0 && w->proj_dim % 8 == 0, RF_ERR_SHAPE, "%s: layers=%d heads=%d hidden=%d inter=%d proj_dim=%d (need hidden %% 8 == 0, <= 4096, "
+             "inter %% 64 == 0, proj_dim %% 8 == 0)", who, w->layers, w->heads, w->hidden, w->inter, w->proj_dim);
   RF_REQUIRE(w->patch > 0 && w->image_size > 0 && w->image_size % w->patch == 0, RF_ERR_SHAPE, "%s: image_size=%d patch=%d", who, w->image_size, w->patch);
   const int g = w->image_size / w->patch, T = g * g + 1;
   RF_REQUIRE(T <= TA_MAXS, RF_ERR_SHAPE, "%s: %d tokens > %d", who, T, TA_MAXS);
   RF_REQUIRE(w->mask_S == (int)round_up(T, 32), RF_ERR_SHAPE, "%s: mask is built for S_pad = %d, %d tokens need %d", who, w->mask_S, T, (int)round_up(T, 32));
-  return RF_OK;
+  return clip_opts_check(o, w->hidden, w->heads, w->mask_S, who);
+}
+
+static const rf_clip_tower_opts CLIP_L_OPTS = {64, RF_CLIP_ACT_QUICK_GELU};
+
+extern "C" int64_t rf_clip_vision_workspace_bytes_opts(const rf_clip_vision_weights* w, const rf_clip_tower_opts* o, int32_t B) {
+  const int rc = vision_check(w, o, "rf_clip_vision_workspace_bytes");
+  if (rc != RF_OK) return rc;
+  RF_REQUIRE(B > 0 && B <= 64, RF_ERR_SHAPE, "rf_clip_vision_workspace_bytes: B=%d (1 .. 64)", B);
+  const int Dp = (int)round_up(w->hidden, 64);
+  return text_sizes(B * w->mask_S, Dp, Dp, w->inter, w->inter).total;
 }
 
 extern "C" int64_t rf_clip_vision_workspace_bytes(const rf_clip_vision_weights* w, int32_t B) {
-  if (vision_check(w, "rf_clip_vision_workspace_bytes") != RF_OK || B <= 0 || B > 64) return RF_ERR_SHAPE;
-  return text_sizes(B * w->mask_S, w->hidden, w->hidden, w->inter, w->inter).total;
+  const int64_t n = rf_clip_vision_workspace_bytes_opts(w, &CLIP_L_OPTS, B);
+  return n < 0 ? RF_ERR_SHAPE : n;
 }
 
 // CLIPVisionModel + visual_projection: patches [B * np][K_pad] -> image_embeds [B][proj_dim].  Workspace use: the patch GEMM's output
-// [B * np][D] lives in QK ([R][2D], R = B * S_pad >= B * np), the post-LN class rows [B][D] in AO.
-extern "C" int rf_clip_vision_encode(const rf_clip_vision_weights* w, const void* patches, int32_t B, void* image_embeds, const rf_workspace* ws,
-                                     void* stream) {
-  RF_TRY(vision_check(w, "rf_clip_vision_encode"));
+// [B * np][D] lives in QK ([R][2D], R = B * S_pad >= B * np), the post-LN class rows [B][Dp] in AO (Dp = D rounded up to the GEMM's
+// K-tile; AO's columns D .. Dp - 1 are zero from text_ctx on: the attention writes D columns per row).
+extern "C" int rf_clip_vision_encode_opts(const rf_clip_vision_weights* w, const rf_clip_tower_opts* o, const void* patches, int32_t B,
+                                          void* image_embeds, const rf_workspace* ws, void* stream) {
+  RF_TRY(vision_check(w, o, "rf_clip_vision_encode"));
   RF_REQUIRE(B > 0 && B <= 64, RF_ERR_SHAPE, "rf_clip_vision_encode: B=%d (1 .. 64)", B);
   RF_REQUIRE(patches && image_embeds && aligned16(patches) && aligned16(image_embeds), RF_ERR_NULL, "rf_clip_vision_encode: NULL / unaligned tensor");
   const int g = w->image_size / w->patch, np = g * g, T = np + 1, S_pad = w->mask_S, D = w->hidden, F = w->inter, R = B * S_pad;
-  const int K_pad = (int)round_up(3 * w->patch * w->patch, 64);
+  const int K_pad = (int)round_up(3 * w->patch * w->patch, 64), Dp = (int)round_up(D, 64);
   hipStream_t st = (hipStream_t)stream;
   TextCtx c;
-  RF_TRY(text_ctx(c, text_sizes(R, D, D, F, F), B, T, S_pad, ws, st, "rf_clip_vision_encode"));
+  RF_TRY(text_ctx(c, text_sizes(R, Dp, Dp, F, F), B, T, S_pad, ws, st, "rf_clip_vision_encode"));
   c.sched = RF_SCHED_TILE256;   // batch invariance: see the file header
   RF_TRY(text_gemm(c, (const bf16_t*)patches, K_pad, w->patch_w, nullptr, B * np, D, K_pad, c.QK, D, RF_EPI_STORE, nullptr));
   {
@@ -228,10 +240,15 @@ extern "C" int rf_clip_vision_encode(const rf_clip_vision_weights* w, const void
     RF_LAUNCH_CHECK();
   }
   RF_TRY(rf_layernorm_modulate(c.Xn, D, c.X, D, R, D, w->pre_ln_scale, w->pre_ln_shift, w->eps, st));   // pre_layrnorm -> residual stream
-  RF_TRY(clip_layers(c, w->layer, w->layers, w->heads, D, F, w->mask, w->eps, "rf_clip_vision_encode"));
-  RF_TRY(rf_layernorm_modulate(c.X, (int64_t)S_pad * D, c.AO, D, B, D, w->post_ln_scale, w->post_ln_shift, w->eps, st));   // row 0 of each image
-  RF_TRY(text_gemm(c, c.AO, D, w->proj, nullptr, B, w->proj_dim, D, (bf16_t*)image_embeds, w->proj_dim, RF_EPI_STORE, nullptr));
+  RF_TRY(clip_layers(c, w->layer, w->layers, w->heads, D, F, w->mask, w->eps, "rf_clip_vision_encode", *o));
+  RF_TRY(rf_layernorm_modulate(c.X, (int64_t)S_pad * D, c.AO, Dp, B, D, w->post_ln_scale, w->post_ln_shift, w->eps, st));   // row 0 of each image
+  RF_TRY(text_gemm(c, c.AO, Dp, w->proj, nullptr, B, w->proj_dim, Dp, (bf16_t*)image_embeds, w->proj_dim, RF_EPI_STORE, nullptr));
   return RF_OK;
+}
+
+extern "C" int rf_clip_vision_encode(const rf_clip_vision_weights* w, const void* patches, int32_t B, void* image_embeds, const rf_workspace* ws,
+                                     void* stream) {
+  return rf_clip_vision_encode_opts(w, &CLIP_L_OPTS, patches, B, image_embeds, ws, stream);
 }
 
 extern "C" int rf_clip_score(const void* img, const void* txt, float logit_scale, float* scores, int32_t B, int32_t P, void* stream) {

@@ -11,7 +11,8 @@
 //     (XOR-swizzled K rows, padded + key-permuted V^T rows), S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_16x16x32_bf16 with P kept
 //     in registers, full-row softmax in fp32 (no running maximum: the whole row of scores is in registers), additive fp32 bias
 //     [heads or 1][S_pad][S_pad] (T5: bucketed relative positions; CLIP: the causal mask; both: -inf on padded keys);
-//   * row kernels (HBM-bound, 16-byte accesses): embedding gather (+ position rows), T5 RMS norm, gelu_new(a) * b, quick_gelu.
+//   * attn80_kernel: the same attention at head dim 80 (the ViT-H/14 towers of PickScore / HPSv2 / LAION CLIP-H), keys <= 480;
+//   * row kernels (HBM-bound, 16-byte accesses): embedding gather (+ position rows), T5 RMS norm, gelu_new(a) * b, quick_gelu, gelu (erf).
 #include "common.hpp"
 #include "text_internal.hpp"
 
@@ -100,6 +101,18 @@ __global__ __launch_bounds__(256) void quick_gelu_kernel(bf16_t* __restrict__ x,
   unpack8(*(const u32x4*)(x + idx * 8), a);
 #pragma unroll
   for (int i = 0; i < 8; ++i) a[i] = a[i] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * a[i]));
+  *(u32x4*)(x + idx * 8) = pack8(a);
+}
+
+// transformers' "gelu" (ViT-H towers), in place: x * 0.5 * (1 + erf(x / sqrt(2))) in fp32, one rounding to bf16 -- the operation order of
+// torch.nn.functional.gelu on a bf16 tensor.  A row kernel of its own, not a GEMM epilogue: the tower runs once per round, not per step.
+__global__ __launch_bounds__(256) void gelu_erf_kernel(bf16_t* __restrict__ x, int64_t n8) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n8) return;
+  float a[8];
+  unpack8(*(const u32x4*)(x + idx * 8), a);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) a[i] = a[i] * 0.5f * (1.0f + erff(a[i] * 0.70710678118654752440f));
   *(u32x4*)(x + idx * 8) = pack8(a);
 }
 
@@ -230,6 +243,156 @@ __global__ __launch_bounds__(256) void attn64_kernel(const bf16_t* __restrict__ 
   }   // it
 }
 
+// ---- attention, head dim 80 (ViT-H/14 vision tower), keys resident in LDS ------------------------------------------------------------
+// Same contract as attn64_kernel (operands, bias, masking, fp32 softmax, fixed reduction order, QI); head dim 80 instead of 64.  It is
+// a kernel of its own and not a template over the head dim: attn64_kernel's results are pinned bit for bit (T5, CLIP-L text, ViT-L
+// vision), so its source stays untouched.  Decisions (MI355X LDS: 64 banks x 4 B, a ds_read_b128 is served in four 16-lane groups,
+// conflict-free when a group's addresses fall on 16 different 16-byte slots of the 256-byte bank row):
+//   * QK^T over 80 = 32 + 32 + 16 channels: three v_mfma_f32_16x16x32_bf16.  The third one's operands hold channels 64 .. 79 in
+//     lane groups g = 0, 1 and ZEROS in g = 2, 3 (those lanes issue no load at all: nothing is read past the head's 80 columns of q
+//     or k).  One instruction shape for the whole kernel and b128 fragment reads only; the half-empty MFMA costs 8 passes per 16
+//     keys in a kernel that is bound by staging K / V^T, not by the matrix pipe.
+//   * K in LDS: a row is 160 B = 10 chunks of 16 B, so (c ^ (r & 7)) over 8 chunks does not carry over -- and nothing is needed in
+//     its place: at the natural pitch of 10 chunks, row r starts at slot 10 r mod 16, which is even and takes 8 values, rows r and
+//     r + 8 sharing one.  A lane group reads its 16 rows with g on rows {0-3, 12-15} and g + 1 on rows {4-11} (or the reverse): of
+//     two rows 8 apart exactly one carries the + 1, so the 16 addresses fall on 16 different slots, for the two whole k-steps and
+//     for the tail alike.  No swizzle, no padding bytes, and the staging copy is linear.  (An odd pitch of 11 chunks is 2-way.)
+//   * V^T in LDS: 80 channel rows, key slots permuted as in attn64_kernel; pitch 64 * m bytes with m = S_pad / 32 made ODD (one
+//     64-byte block of padding when it is even) and the 16-byte chunk g of a 64-byte key block stored at g ^ swz((d & 15) >> 2),
+//     swz = {0, 2, 3, 1}.  Rows d, d + 4, d + 8, d + 12 of a 16-row fragment share a 64-byte quarter of the bank row (m odd: 4 m d mod
+//     16 walks the four quarters with d mod 4) and carry g, g ^ 1, g ^ 1, g within a lane group; the swizzle sends them to four
+//     different chunks.  (attn64_kernel's pitch S_pad * 2 + 16 is 2-way under the same model.)
+//   * PV: 5 output tiles of 16 channels, P in registers.
+//   * LDS budget: S_pad * 160 + 80 * 64 * (m | 1) bytes: 92,160 B at S_pad = 288 (257 tokens of ViT-H/14 at 224 px), 153,600 B at
+//     S_pad = 480 = TA80_MAXS, the largest multiple of 32 that fits a CU's 160 KiB (512 keys would need 168,960 B).  Larger towers
+//     are refused by the entry points; there is no streaming-keys variant.
+//   * q scale: the binding folds 1/sqrt(80) into the q weights and bias, `scale` is 1.
+// tests/test_clip_h_cpu.py restates the three fragment-read address formulas against the bank model.
+constexpr int TA80_NT = TA80_MAXS / 16;
+static inline int ta80_vpitch(int S_pad) { return 64 * ((S_pad >> 5) | 1); }
+static inline int ta80_lds_bytes(int S_pad) { return S_pad * 160 + 80 * ta80_vpitch(S_pad); }
+static_assert(TA80_MAXS % 32 == 0 && TA80_MAXS * 160 + 80 * 64 * ((TA80_MAXS / 32) | 1) <= 160 * 1024, "head-dim-80 K + V^T must fit the LDS");
+
+template <int QI>
+__global__ __launch_bounds__(256) void attn80_kernel(const bf16_t* __restrict__ q, int64_t ldq, const bf16_t* __restrict__ k, int64_t ldk,
+                                                     const bf16_t* __restrict__ vt, int64_t ldvt, const float* __restrict__ bias, int64_t bias_hs,
+                                                     bf16_t* __restrict__ out, int64_t ldo, int S, int S_pad, float scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const kl = smem;                       // K rows: 160 B each, as they lie in memory
+  char* const vl = smem + S_pad * 160;         // V^T rows: pitch 64 * odd, chunk g of a key block at g ^ swz, key slots permuted
+  const int vpitch = 64 * ((S_pad >> 5) | 1);
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int l15 = lane & 15, g = lane >> 4;
+  const int head = blockIdx.y, qb = blockIdx.x;
+  {
+    const int64_t r0 = (int64_t)blockIdx.z * S_pad;
+    q += r0 * ldq; k += r0 * ldk; vt += r0; out += r0 * ldo;
+  }
+  // ---- stage the head's K and V^T --------------------------------------------------------------------------------------------
+  for (int idx = tid; idx < S_pad * 10; idx += 256) {
+    const int r = idx / 10, c = idx - r * 10;
+    *(u32x4*)(kl + idx * 16) = *(const u32x4*)(k + (int64_t)r * ldk + head * 80 + c * 8);
+  }
+  // key slots of a 32-key block as in attn64_kernel: slot(key) = 8 (key%16 / 4) + 4 (key / 16) + key % 4
+  const int kc = S_pad >> 3;
+  for (int idx = tid; idx < 80 * kc; idx += 256) {
+    const int d = idx / kc, m = idx - d * kc;
+    const u32x4 v = *(const u32x4*)(vt + (int64_t)(head * 80 + d) * ldvt + m * 8);
+    const int blk = (m * 8) >> 5, kap = (m * 8) & 31;
+    const int tile = kap >> 4, g0 = (kap & 15) >> 2;
+    const int sw = (0x78 >> (2 * ((d & 15) >> 2))) & 3;
+    char* dst = vl + d * vpitch + blk * 64 + 8 * tile;
+    u32x2 lo, hi;
+    lo[0] = v[0]; lo[1] = v[1]; hi[0] = v[2]; hi[1] = v[3];
+    *(u32x2*)(dst + ((g0 ^ sw) << 4)) = lo;
+    *(u32x2*)(dst + (((g0 + 1) ^ sw) << 4)) = hi;
+  }
+  __syncthreads();
+  const int nt = S_pad >> 4;
+  const float LOG2E = 1.4426950408889634f;
+  const float sl2 = scale * LOG2E;
+  const int vsw = (0x78 >> (2 * (l15 >> 2))) & 3;   // every V^T fragment row is 16 dt + l15
+  const bf16x8 zero8 = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+#pragma unroll 1
+  for (int it = 0; it < QI; ++it) {
+  // ---- scores: S^T tile t = K[16t .. 16t+15] Q^T: this lane holds keys 16t + 4g + r of query l15 ---------------------------------
+  const int q_row = (qb * QI + it) * 64 + w * 16 + l15;
+  if ((qb * QI + it) * 64 >= S_pad) break;
+  const int q_ld = q_row < S_pad ? q_row : S_pad - 1;
+  bf16x8 qf[3];
+#pragma unroll
+  for (int ds = 0; ds < 2; ++ds) qf[ds] = *(const bf16x8*)(q + (int64_t)q_ld * ldq + head * 80 + ds * 32 + g * 8);
+  qf[2] = zero8;
+  if (g < 2) qf[2] = *(const bf16x8*)(q + (int64_t)q_ld * ldq + head * 80 + 64 + g * 8);
+  const float* brow = bias ? bias + head * bias_hs + (int64_t)q_ld * S_pad + 4 * g : nullptr;
+  f32x4 s[TA80_NT];
+  float mx = -__builtin_huge_valf();
+#pragma unroll
+  for (int t = 0; t < TA80_NT; ++t) {
+    if (t < nt) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      const int r = t * 16 + l15;
+#pragma unroll
+      for (int ds = 0; ds < 2; ++ds) {
+        const bf16x8 kf = *(const bf16x8*)(kl + r * 160 + ((ds * 4 + g) << 4));
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ds], acc, 0, 0, 0);
+      }
+      bf16x8 kf2 = zero8;
+      if (g < 2) kf2 = *(const bf16x8*)(kl + r * 160 + ((8 + g) << 4));
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf2, qf[2], acc, 0, 0, 0);
+      f32x4 b = {0.f, 0.f, 0.f, 0.f};
+      if (brow) b = *(const f32x4*)(brow + t * 16);
+#pragma unroll
+      for (int r2 = 0; r2 < 4; ++r2) {
+        acc[r2] = acc[r2] * sl2 + b[r2] * LOG2E;
+        mx = fmaxf(mx, acc[r2]);
+      }
+      s[t] = acc;
+    }
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 16));
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  if (!(mx > -__builtin_huge_valf())) mx = 0.f;   // a fully masked (padded) query row: keep the arithmetic finite
+  // ---- P = exp2(s - max), row sums, O^T += V^T P^T per 32-key block ------------------------------------------------------------------
+  f32x4 oacc[5];
+#pragma unroll
+  for (int dt = 0; dt < 5; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float l = 0.f;
+#pragma unroll
+  for (int b = 0; b < TA80_NT / 2; ++b) {
+    if (2 * b < nt) {
+      float p[8];
+#pragma unroll
+      for (int r2 = 0; r2 < 4; ++r2) {
+        p[r2] = __builtin_amdgcn_exp2f(s[2 * b][r2] - mx);
+        p[4 + r2] = __builtin_amdgcn_exp2f(s[2 * b + 1][r2] - mx);
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) l += p[i];
+      const bf16x8 pf = __builtin_bit_cast(bf16x8, pack8(p));
+#pragma unroll
+      for (int dt = 0; dt < 5; ++dt) {
+        const bf16x8 vf = *(const bf16x8*)(vl + (dt * 16 + l15) * vpitch + b * 64 + ((g ^ vsw) << 4));
+        oacc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, oacc[dt], 0, 0, 0);
+      }
+    }
+  }
+  l += __shfl_xor(l, 16);
+  l += __shfl_xor(l, 32);
+  if (q_row < S) {
+    const float inv = 1.0f / l;
+    bf16_t* orow = out + (int64_t)q_row * ldo + head * 80 + 4 * g;
+#pragma unroll
+    for (int dt = 0; dt < 5; ++dt) {
+      u32x2 v;
+      v[0] = pack2(oacc[dt][0] * inv, oacc[dt][1] * inv);
+      v[1] = pack2(oacc[dt][2] * inv, oacc[dt][3] * inv);
+      *(u32x2*)(orow + dt * 16) = v;
+    }
+  }
+  }   // it
+}
+
 // ---- host side (TextCtx / TextSizes: text_internal.hpp) ------------------------------------------------------------------------
 int text_ctx(TextCtx& c, const TextSizes& z, int B, int S, int S_pad, const rf_workspace* ws, hipStream_t st, const char* who) {
   RF_REQUIRE(ws && ws->base && aligned16(ws->base) && ws->bytes >= z.total, RF_ERR_WORKSPACE, "%s: workspace %lld < required %lld bytes", who,
@@ -295,29 +458,74 @@ int text_attention(TextCtx& c, int heads, int inner, const float* bias, int64_t 
   return RF_OK;
 }
 
+// head dim 80: q | k [R][2 * inner], V^T [inner][R], out [R][ld_ao] (ld_ao = inner rounded up to the GEMM's K-tile, see clip_layers)
+int text_attention80(TextCtx& c, int heads, int inner, int64_t ld_ao, const float* bias, int64_t bias_hs, float scale) {
+  RF_REQUIRE(c.S_pad <= TA80_MAXS, RF_ERR_SHAPE, "head-dim-80 attention: S_pad=%d > %d keys (K and V^T stay resident in the 160 KiB LDS)", c.S_pad,
+             TA80_MAXS);
+  const int lds = ta80_lds_bytes(c.S_pad);
+  static bool attr = false;
+  if (!attr) {
+    RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn80_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, ta80_lds_bytes(TA80_MAXS)));
+    RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn80_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, ta80_lds_bytes(TA80_MAXS)));
+    attr = true;
+  }
+  const bool wide = (int64_t)heads * c.B * cdiv(c.S_pad, 256) >= 256;   // as text_attention; regroups query tiles only (batch invariance)
+  ProfScope prof(RF_KC_ATTN, 4.0 * (double)c.S_pad * c.S_pad * 80.0 * heads * c.B, c.st);
+  if (wide)
+    hipLaunchKernelGGL(attn80_kernel<4>, dim3(cdiv(c.S_pad, 256), heads, c.B), dim3(256), lds, c.st, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner,
+                       c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO, ld_ao, c.S, c.S_pad, scale);
+  else
+    hipLaunchKernelGGL(attn80_kernel<1>, dim3(cdiv(c.S_pad, 64), heads, c.B), dim3(256), lds, c.st, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner,
+                       c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO, ld_ao, c.S, c.S_pad, scale);
+  RF_LAUNCH_CHECK();
+  return RF_OK;
+}
+
 // The pre-LN CLIP encoder layers over the residual stream c.X (B sequences of S_pad rows, width D, MLP width F): shared by the text
 // tower (causal mask) and the vision tower (padded keys masked).  Every GEMM goes through text_gemm, i.e. c.sched decides the schedule.
-int clip_layers(TextCtx& c, const rf_clip_layer* layer, int layers, int heads, int D, int F, const float* mask, float eps, const char* who) {
-  const int R = c.B * c.S_pad;
+// o: head dim (64 | 80) and activation (validated by clip_opts_check).  Dp = D rounded up to the GEMM's 64-element K-tile: the
+// operands whose K axis is the hidden width (Xn, AO; the weights, packed by the binding) have row pitch Dp and zeros in columns
+// D .. Dp - 1.  Dp == D for every hidden width that is a multiple of 64 (all head-dim-64 towers, ViT-H's 1280): nothing moves there.
+int clip_layers(TextCtx& c, const rf_clip_layer* layer, int layers, int heads, int D, int F, const float* mask, float eps, const char* who,
+                const rf_clip_tower_opts& o) {
+  const int R = c.B * c.S_pad, Dp = (int)round_up(D, 64);
   hipStream_t st = c.st;
+  if (Dp != D) RF_CHECK_HIP(hipMemsetAsync(c.Xn, 0, (size_t)R * Dp * 2, st));   // the pad columns of Xn: LayerNorm writes D columns per row
   for (int i = 0; i < layers; ++i) {
     const rf_clip_layer& L = layer[i];
     RF_REQUIRE(L.ln1_scale && L.ln1_shift && L.w_qk && L.b_qk && L.w_v && L.w_o && L.b_o && L.ln2_scale && L.ln2_shift && L.w_fc1 && L.b_fc1 && L.w_fc2 &&
                    L.b_fc2, RF_ERR_NULL, "%s: layer %d has NULL weights", who, i);
-    RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, D, R, D, L.ln1_scale, L.ln1_shift, eps, st));
-    RF_TRY(text_gemm(c, c.Xn, D, L.w_qk, L.b_qk, R, 2 * D, D, c.QK, 2 * D, RF_EPI_STORE, nullptr));
-    RF_TRY(text_gemm(c, (const bf16_t*)L.w_v, D, c.Xn, nullptr, D, R, D, c.VT, R, RF_EPI_STORE, nullptr));
-    RF_TRY(text_attention(c, heads, D, mask, 0, 1.0f));
-    RF_TRY(text_gemm(c, c.AO, D, L.w_o, L.b_o, R, D, D, c.X, D, RF_EPI_STORE, c.X));
-    RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, D, R, D, L.ln2_scale, L.ln2_shift, eps, st));
-    RF_TRY(text_gemm(c, c.Xn, D, L.w_fc1, L.b_fc1, R, F, D, c.HID, F, RF_EPI_STORE, nullptr));
+    RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, Dp, R, D, L.ln1_scale, L.ln1_shift, eps, st));
+    RF_TRY(text_gemm(c, c.Xn, Dp, L.w_qk, L.b_qk, R, 2 * D, Dp, c.QK, 2 * D, RF_EPI_STORE, nullptr));
+    RF_TRY(text_gemm(c, (const bf16_t*)L.w_v, Dp, c.Xn, nullptr, D, R, Dp, c.VT, R, RF_EPI_STORE, nullptr));
+    if (o.head_dim == 64) RF_TRY(text_attention(c, heads, D, mask, 0, 1.0f));
+    else RF_TRY(text_attention80(c, heads, D, Dp, mask, 0, 1.0f));
+    RF_TRY(text_gemm(c, c.AO, Dp, L.w_o, L.b_o, R, D, Dp, c.X, D, RF_EPI_STORE, c.X));
+    RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, Dp, R, D, L.ln2_scale, L.ln2_shift, eps, st));
+    RF_TRY(text_gemm(c, c.Xn, Dp, L.w_fc1, L.b_fc1, R, F, Dp, c.HID, F, RF_EPI_STORE, nullptr));
     {
       ProfScope prof(RF_KC_ROWOP, (double)R * F * 4, st);
-      hipLaunchKernelGGL(quick_gelu_kernel, dim3(grid_for((int64_t)R * F / 8)), dim3(256), 0, st, c.HID, (int64_t)R * F / 8);
+      if (o.act == RF_CLIP_ACT_GELU)
+        hipLaunchKernelGGL(gelu_erf_kernel, dim3(grid_for((int64_t)R * F / 8)), dim3(256), 0, st, c.HID, (int64_t)R * F / 8);
+      else
+        hipLaunchKernelGGL(quick_gelu_kernel, dim3(grid_for((int64_t)R * F / 8)), dim3(256), 0, st, c.HID, (int64_t)R * F / 8);
       RF_LAUNCH_CHECK();
     }
     RF_TRY(text_gemm(c, c.HID, F, L.w_fc2, L.b_fc2, R, D, F, c.X, D, RF_EPI_STORE, c.X));
   }
+  return RF_OK;
+}
+
+// head dim and activation of a CLIP tower + what they demand of its geometry; S_pad: the keys of one attention call
+int clip_opts_check(const rf_clip_tower_opts* o, int hidden, int heads, int S_pad, const char* who) {
+  RF_REQUIRE(o, RF_ERR_NULL, "%s: opts NULL", who);
+  RF_REQUIRE(o->head_dim == 64 || o->head_dim == 80, RF_ERR_UNSUPPORTED, "%s: head_dim=%d (attention kernels exist for 64 and 80)", who, o->head_dim);
+  RF_REQUIRE(o->act == RF_CLIP_ACT_QUICK_GELU || o->act == RF_CLIP_ACT_GELU, RF_ERR_UNSUPPORTED, "%s: act=%d (0 = quick_gelu, 1 = gelu)", who, o->act);
+  RF_REQUIRE(heads > 0 && hidden == heads * o->head_dim && hidden <= 4096, RF_ERR_SHAPE, "%s: hidden=%d heads=%d head_dim=%d (need hidden = heads * head_dim <= 4096)",
+             who, hidden, heads, o->head_dim);
+  const int lim = o->head_dim == 64 ? TA_MAXS : TA80_MAXS;
+  RF_REQUIRE(S_pad <= lim, RF_ERR_SHAPE, "%s: S_pad=%d > %d keys, the limit at head_dim %d (K and V^T of a head stay resident in the 160 KiB LDS)", who,
+             S_pad, lim, o->head_dim);
   return RF_OK;
 }
 
@@ -391,51 +599,75 @@ extern "C" int rf_t5_encode(const rf_t5_weights* w, const int32_t* ids, int32_t 
   return RF_OK;
 }
 
-static int clip_check(const rf_clip_weights* w, int32_t S, const char* who) {
+static int clip_check(const rf_clip_weights* w, const rf_clip_tower_opts* o, int32_t S, const char* who) {
   RF_REQUIRE(w && w->layer && w->tok_embed && w->pos_embed && w->final_ln_scale && w->final_ln_shift, RF_ERR_NULL, "%s: weights NULL", who);
-  RF_REQUIRE(w->layers > 0 && w->heads > 0 && w->hidden == w->heads * 64 && w->hidden % 64 == 0 && w->hidden <= 4096 && w->inter > 0 && w->inter % 64 == 0,
-             RF_ERR_SHAPE, "%s: layers=%d heads=%d hidden=%d inter=%d (need hidden = 64 * heads <= 4096, inter %% 64 == 0)", who, w->layers, w->heads,
-             w->hidden, w->inter);
+  RF_REQUIRE(w->layers > 0 && w->heads > 0 && w->hidden > 0 && w->hidden % 8 == 0 && w->hidden <= 4096 && w->inter > 0 && w->inter % 64 == 0, RF_ERR_SHAPE,
+             "%s: layers=%d heads=%d hidden=%d inter=%d (need hidden %% 8 == 0, <= 4096, inter %% 64 == 0)", who, w->layers, w->heads, w->hidden, w->inter);
   RF_REQUIRE(S > 0 && S <= w->max_pos && S <= TA_MAXS, RF_ERR_SHAPE, "%s: S=%d (1 .. min(max_pos = %d, %d))", who, S, w->max_pos, TA_MAXS);
-  return RF_OK;
+  return clip_opts_check(o, w->hidden, w->heads, (int)round_up(S, 32), who);
+}
+
+static const rf_clip_tower_opts CLIP_L_OPTS = {64, RF_CLIP_ACT_QUICK_GELU};
+
+extern "C" int64_t rf_clip_text_workspace_bytes_opts(const rf_clip_weights* w, const rf_clip_tower_opts* o, int32_t B, int32_t S) {
+  const int rc = clip_check(w, o, S, "rf_clip_text_workspace_bytes");
+  if (rc != RF_OK) return rc;
+  RF_REQUIRE(B > 0 && B <= 64, RF_ERR_SHAPE, "rf_clip_text_workspace_bytes: B=%d (1 .. 64)", B);
+  const int S_pad = (int)round_up(S, 32), Dp = (int)round_up(w->hidden, 64);
+  return text_sizes(B * S_pad, Dp, Dp, w->inter, w->inter).total;
 }
 
 extern "C" int64_t rf_clip_text_workspace_bytes(const rf_clip_weights* w, int32_t B, int32_t S) {
-  if (clip_check(w, S, "rf_clip_text_workspace_bytes") != RF_OK || B <= 0 || B > 64) return RF_ERR_SHAPE;
-  const int S_pad = (int)round_up(S, 32);
-  return text_sizes(B * S_pad, w->hidden, w->hidden, w->inter, w->inter).total;
+  const int64_t n = rf_clip_text_workspace_bytes_opts(w, &CLIP_L_OPTS, B, S);
+  return n < 0 ? RF_ERR_SHAPE : n;
 }
 
 // CLIPTextModel(ids) for B sequences of S tokens: last_hidden_state [B][S][hidden] (final LayerNorm applied; may be NULL) and
 // pooler_output [B][hidden] = the final-normed row eos_pos[b] of sequence b (HOST array; the binding finds the positions: argmax(ids)
 // for the legacy eos_token_id == 2 config, else the first eos_token_id).  mask: [S_pad][S_pad] fp32, 0 on and below the diagonal,
-// -inf above it and in the columns of padded keys.  The binding folds 1/sqrt(64) into w_q / b_q, writes LayerNorm weights as
+// -inf above it and in the columns of padded keys.  The binding folds 1/sqrt(head_dim) into w_q / b_q, writes LayerNorm weights as
 // (weight - 1, bias) pairs for rf_layernorm_modulate and folds v_proj.bias into the out-projection bias (softmax rows sum to 1).
-extern "C" int rf_clip_text_encode(const rf_clip_weights* w, const int32_t* ids, int32_t B, int32_t S, const int32_t* eos_pos, void* last_hidden,
-                                   void* pooled, const rf_workspace* ws, void* stream) {
-  RF_TRY(clip_check(w, S, "rf_clip_text_encode"));
+extern "C" int rf_clip_text_encode_opts(const rf_clip_weights* w, const rf_clip_tower_opts* o, const int32_t* ids, int32_t B, int32_t S,
+                                        const int32_t* eos_pos, void* last_hidden, void* pooled, const rf_workspace* ws, void* stream) {
+  RF_TRY(clip_check(w, o, S, "rf_clip_text_encode"));
   RF_REQUIRE(B > 0 && B <= 64, RF_ERR_SHAPE, "rf_clip_text_encode: B=%d (1 .. 64)", B);
   RF_REQUIRE(ids && (last_hidden || pooled) && (eos_pos || !pooled), RF_ERR_NULL, "rf_clip_text_encode: NULL tensor");
   if (pooled)
     for (int b = 0; b < B; ++b)
       RF_REQUIRE(eos_pos[b] >= 0 && eos_pos[b] < S, RF_ERR_SHAPE, "rf_clip_text_encode: eos_pos[%d]=%d outside 0 .. %d", b, eos_pos[b], S - 1);
-  const int S_pad = (int)round_up(S, 32), D = w->hidden, F = w->inter, R = B * S_pad;
+  const int S_pad = (int)round_up(S, 32), D = w->hidden, Dp = (int)round_up(D, 64), F = w->inter, R = B * S_pad;
   RF_REQUIRE(w->mask && w->mask_S == S_pad, RF_ERR_SHAPE, "rf_clip_text_encode: mask is built for S_pad = %d, this call needs %d", w->mask_S, S_pad);
   hipStream_t st = (hipStream_t)stream;
   TextCtx c;
-  RF_TRY(text_ctx(c, text_sizes(R, D, D, F, F), B, S, S_pad, ws, st, "rf_clip_text_encode"));
+  RF_TRY(text_ctx(c, text_sizes(R, Dp, Dp, F, F), B, S, S_pad, ws, st, "rf_clip_text_encode"));
   {
     ProfScope prof(RF_KC_ROWOP, (double)R * D * 6, st);
     hipLaunchKernelGGL(embed_rows_kernel, dim3(grid_for((int64_t)R * D / 8)), dim3(256), 0, st, (const bf16_t*)w->tok_embed, (const bf16_t*)w->pos_embed,
                        ids, c.X, S, S_pad, R, D, w->vocab);
     RF_LAUNCH_CHECK();
   }
-  RF_TRY(clip_layers(c, w->layer, w->layers, w->heads, D, F, w->mask, w->eps, "rf_clip_text_encode"));
+  RF_TRY(clip_layers(c, w->layer, w->layers, w->heads, D, F, w->mask, w->eps, "rf_clip_text_encode", *o));
   RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, D, R, D, w->final_ln_scale, w->final_ln_shift, w->eps, st));
   for (int b = 0; b < B; ++b) {
     const bf16_t* src = c.Xn + (int64_t)b * S_pad * D;
     if (last_hidden) RF_CHECK_HIP(hipMemcpyAsync((char*)last_hidden + (int64_t)b * S * D * 2, src, (size_t)S * D * 2, hipMemcpyDeviceToDevice, st));
     if (pooled) RF_CHECK_HIP(hipMemcpyAsync((char*)pooled + (int64_t)b * D * 2, src + (int64_t)eos_pos[b] * D, (size_t)D * 2, hipMemcpyDeviceToDevice, st));
   }
+  return RF_OK;
+}
+
+extern "C" int rf_clip_text_encode(const rf_clip_weights* w, const int32_t* ids, int32_t B, int32_t S, const int32_t* eos_pos, void* last_hidden,
+                                   void* pooled, const rf_workspace* ws, void* stream) {
+  return rf_clip_text_encode_opts(w, &CLIP_L_OPTS, ids, B, S, eos_pos, last_hidden, pooled, ws, stream);
+}
+
+// The activation of the ViT-H towers on its own (tests; a binding that runs an MLP of its own): x[0 .. n) in place, n % 8 == 0
+extern "C" int rf_gelu_erf_inplace(void* x, int64_t n, void* stream) {
+  RF_REQUIRE(x && aligned16(x), RF_ERR_NULL, "rf_gelu_erf_inplace: NULL / unaligned tensor");
+  RF_REQUIRE(n > 0 && n % 8 == 0 && n / 8 / 256 < 0x7fffffffll, RF_ERR_SHAPE, "rf_gelu_erf_inplace: n=%lld (a positive multiple of 8)", (long long)n);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope prof(RF_KC_ROWOP, (double)n * 4, st);
+  hipLaunchKernelGGL(gelu_erf_kernel, dim3(grid_for(n / 8)), dim3(256), 0, st, (bf16_t*)x, n / 8);
+  RF_LAUNCH_CHECK();
   return RF_OK;
 }

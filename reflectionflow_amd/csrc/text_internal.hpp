@@ -1,5 +1,5 @@
 // Internal interface of text.hip shared with clip_vision.hip (not part of the C ABI): the encoder context over a caller-owned
-// workspace, the projection GEMM, the head-dim-64 attention and the pre-LN CLIP layer loop.  The text towers keep their shape-based
+// workspace, the projection GEMM, the head-dim-64 / -80 attention and the pre-LN CLIP layer loop.  The text towers keep their shape-based
 // GEMM policy (TextCtx::sched = RF_SCHED_AUTO); the vision tower pins one schedule for every projection (clip_vision.hip).
 #pragma once
 #include "common.hpp"
@@ -14,7 +14,8 @@
 
 namespace rf {
 
-constexpr int TA_MAXS = 512;   // keys of attn64_kernel
+constexpr int TA_MAXS = 512;     // keys of attn64_kernel
+constexpr int TA80_MAXS = 480;   // keys of attn80_kernel (text.hip: K + V^T of a head at head dim 80 within the 160 KiB LDS)
 
 struct TextCtx {
   hipStream_t st;
@@ -43,6 +44,9 @@ int text_ctx(TextCtx& c, const TextSizes& z, int B, int S, int S_pad, const rf_w
 int text_gemm(TextCtx& c, const bf16_t* x, int64_t ldx, const void* w, const void* b, int M, int N, int K, bf16_t* y, int64_t ldy, int epi,
               const bf16_t* residual);
 int text_attention(TextCtx& c, int heads, int inner, const float* bias, int64_t bias_hs, float scale);
-int clip_layers(TextCtx& c, const rf_clip_layer* layer, int layers, int heads, int D, int F, const float* mask, float eps, const char* who);
+int text_attention80(TextCtx& c, int heads, int inner, int64_t ld_ao, const float* bias, int64_t bias_hs, float scale);
+int clip_layers(TextCtx& c, const rf_clip_layer* layer, int layers, int heads, int D, int F, const float* mask, float eps, const char* who,
+                const rf_clip_tower_opts& o);
+int clip_opts_check(const rf_clip_tower_opts* o, int hidden, int heads, int S_pad, const char* who);
 
 }  // namespace rf

@@ -10,8 +10,8 @@ text_encoder/model.safetensors load unchanged, with or without the `text_model.`
 `pipe.text_encoder` callable of flux/pipeline.py (prompt -> (prompt_embeds, pooled)) once a tokenizer callable is supplied --
 vocabulary files are host-side data this repo does not ship.  No CPU fallback: CPU tensors or a missing library raise.
 
-What stays in PyTorch is plumbing only: the weight repacking done once here (q|k and wi_0|wi_1 concatenated, 1/sqrt(64) folded into
-CLIP's q projection, LayerNorm weights as (w - 1, b), v bias folded into the out-projection bias) and the integer work of the
+What stays in PyTorch is plumbing only: the weight repacking done once here (q|k and wi_0|wi_1 concatenated, 1/sqrt(head_dim) folded
+into CLIP's q projection, LayerNorm weights as (w - 1, b), v bias folded into the out-projection bias) and the integer work of the
 attention biases (T5's relative-position buckets gathered once per sequence length; CLIP's causal mask).
 """
 from __future__ import annotations
@@ -30,6 +30,19 @@ BF = torch.bfloat16
 
 def _pad32(n: int) -> int:
     return (n + 31) // 32 * 32
+
+
+def _tower_opts(who: str, hidden: int, num_heads: int, head_dim: int, act: str) -> "L.rf_clip_tower_opts":
+    """rf_clip_tower_opts of a CLIP tower: head dim 64 (CLIP-L) or 80 (ViT-H/14 vision), activation "quick_gelu" or "gelu" (erf)."""
+    if head_dim not in (64, 80):
+        raise RFError(f"{who}: head dim {head_dim}: attention kernels exist for head dims 64 and 80")
+    if hidden != head_dim * num_heads:
+        raise RFError(f"{who}: hidden {hidden} with {num_heads} heads is not a head dim of {head_dim}")
+    if act not in L.CLIP_ACTS:
+        raise RFError(f"{who}: hidden_act {act!r} (one of {sorted(L.CLIP_ACTS)})")
+    o = L.rf_clip_tower_opts()
+    o.head_dim, o.act = head_dim, L.CLIP_ACTS[act]
+    return o
 
 
 def t5_relative_position_bucket(rel: torch.Tensor, num_buckets: int = 32, max_distance: int = 128) -> torch.Tensor:
@@ -140,9 +153,10 @@ class HipT5Encoder:
 
 
 class HipClipTextEncoder:
-    """CLIPTextModel (pre-LN blocks, causal mask, quick_gelu): last_hidden_state and pooler_output."""
+    """CLIPTextModel (pre-LN blocks, causal mask, quick_gelu or gelu): last_hidden_state and pooler_output."""
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], num_heads: int, device, eos_token_id: int = 2, eps: float = 1e-5):
+    def __init__(self, state_dict: Dict[str, torch.Tensor], num_heads: int, device, eos_token_id: int = 2, eps: float = 1e-5,
+                 head_dim: int = 64, act: str = "quick_gelu"):
         device = torch.device(device)
         if device.type != "cuda":
             raise RFError(f"HipClipTextEncoder: device {device}; the HIP path has no CPU fallback")
@@ -154,12 +168,11 @@ class HipClipTextEncoder:
         if n_layers == 0:
             raise RFError("HipClipTextEncoder: no encoder.layers.* keys in the state dict")
         D = sd["embeddings.token_embedding.weight"].shape[1]
-        if D != 64 * num_heads:
-            raise RFError(f"HipClipTextEncoder: hidden {D} with {num_heads} heads: the attention kernel is built for a head dim of 64")
+        self._opts = _tower_opts("HipClipTextEncoder", D, num_heads, head_dim, act)
         self.device, self.heads, self.hidden, self.eos_token_id = device, num_heads, D, eos_token_id
         k = self._k = _Keep(device)
         f = lambda t: t.detach().float()  # noqa: E731
-        self._layers = _clip_layers(k, sd, n_layers)
+        self._layers = _clip_layers(k, sd, n_layers, head_dim)
         w = self._w = L.rf_clip_weights()
         w.layers, w.hidden, w.heads, w.inter = n_layers, D, num_heads, sd["encoder.layers.0.mlp.fc1.weight"].shape[0]
         w.vocab, w.max_pos, w.eps = sd["embeddings.token_embedding.weight"].shape[0], sd["embeddings.position_embedding.weight"].shape[0], eps
@@ -199,10 +212,12 @@ class HipClipTextEncoder:
             pooled = torch.empty(B, self.hidden, dtype=BF, device=self.device)
         for b0 in range(0, B, 64):
             nb = min(64, B - b0)
-            ws = self._ws.get(lib.rf_clip_text_workspace_bytes(C.byref(w), nb, S))
+            o = C.byref(self._opts)
+            ws = self._ws.get(_ws_bytes(lib.rf_clip_text_workspace_bytes_opts(C.byref(w), o, nb, S), "rf_clip_text_workspace_bytes_opts"))
             pos_h = (C.c_int32 * nb)(*[int(e) for e in eos[b0:b0 + nb]]) if pool_in_library else None
-            L.check(lib.rf_clip_text_encode(C.byref(w), ids32[b0].data_ptr(), nb, S, pos_h, last[b0].data_ptr(),
-                                            pooled[b0].data_ptr() if pool_in_library else None, C.byref(ws), stream_ptr()), "rf_clip_text_encode")
+            L.check(lib.rf_clip_text_encode_opts(C.byref(w), o, ids32[b0].data_ptr(), nb, S, pos_h, last[b0].data_ptr(),
+                                                 pooled[b0].data_ptr() if pool_in_library else None, C.byref(ws), stream_ptr()),
+                    "rf_clip_text_encode_opts")
         if pool_in_library:
             return last, pooled
         # pooler_output = the final-normed row at the EOS position: a device-side gather (no host sync; the C entry point takes host
@@ -212,22 +227,36 @@ class HipClipTextEncoder:
         return last, pooled
 
 
-def _clip_layers(k: "_Keep", sd: Dict[str, torch.Tensor], n_layers: int) -> "C.Array":
-    """rf_clip_layer records of a CLIP encoder (text or vision tower: the same pre-LN layer): q|k concatenated with 1/sqrt(64) folded
-    into q, LayerNorm weights as (w - 1, b), v_proj.bias folded into the out-projection bias (softmax rows sum to 1)."""
+def _ws_bytes(n: int, what: str) -> int:
+    """a workspace size query's answer, or the library's message for its refusal"""
+    if n < 0:
+        L.check(int(n), what)
+    return n
+
+
+def _kpad(w: torch.Tensor) -> torch.Tensor:
+    """[N, K] -> [N, round_up(K, 64)], zero-padded: the GEMM walks K in 64-element tiles (a no-op for every real tower's width)."""
+    K = w.shape[1]
+    return w if K % 64 == 0 else torch.nn.functional.pad(w, (0, (K + 63) // 64 * 64 - K))
+
+
+def _clip_layers(k: "_Keep", sd: Dict[str, torch.Tensor], n_layers: int, head_dim: int = 64) -> "C.Array":
+    """rf_clip_layer records of a CLIP encoder (text or vision tower: the same pre-LN layer): q|k concatenated with 1/sqrt(head_dim)
+    folded into q, LayerNorm weights as (w - 1, b), v_proj.bias folded into the out-projection bias (softmax rows sum to 1)."""
     f = lambda t: t.detach().float()  # noqa: E731
+    qs = 0.125 if head_dim == 64 else head_dim ** -0.5
     layers = (L.rf_clip_layer * n_layers)()
     for i in range(n_layers):
         p = f"encoder.layers.{i}."
         y = layers[i]
         y.ln1_scale, y.ln1_shift = k.t(f(sd[p + "layer_norm1.weight"]) - 1.0), k.t(sd[p + "layer_norm1.bias"])
         y.ln2_scale, y.ln2_shift = k.t(f(sd[p + "layer_norm2.weight"]) - 1.0), k.t(sd[p + "layer_norm2.bias"])
-        y.w_qk = k.t(torch.cat([f(sd[p + "self_attn.q_proj.weight"]) * 0.125, f(sd[p + "self_attn.k_proj.weight"])], 0))
-        y.b_qk = k.t(torch.cat([f(sd[p + "self_attn.q_proj.bias"]) * 0.125, f(sd[p + "self_attn.k_proj.bias"])], 0))
-        y.w_v = k.t(sd[p + "self_attn.v_proj.weight"])
+        y.w_qk = k.t(_kpad(torch.cat([f(sd[p + "self_attn.q_proj.weight"]) * qs, f(sd[p + "self_attn.k_proj.weight"])], 0)))
+        y.b_qk = k.t(torch.cat([f(sd[p + "self_attn.q_proj.bias"]) * qs, f(sd[p + "self_attn.k_proj.bias"])], 0))
+        y.w_v = k.t(_kpad(sd[p + "self_attn.v_proj.weight"]))
         wo = f(sd[p + "self_attn.out_proj.weight"])
-        y.w_o, y.b_o = k.t(wo), k.t(f(sd[p + "self_attn.out_proj.bias"]) + wo @ f(sd[p + "self_attn.v_proj.bias"]))
-        y.w_fc1, y.b_fc1 = k.t(sd[p + "mlp.fc1.weight"]), k.t(sd[p + "mlp.fc1.bias"])
+        y.w_o, y.b_o = k.t(_kpad(wo)), k.t(f(sd[p + "self_attn.out_proj.bias"]) + wo @ f(sd[p + "self_attn.v_proj.bias"]))
+        y.w_fc1, y.b_fc1 = k.t(_kpad(sd[p + "mlp.fc1.weight"])), k.t(sd[p + "mlp.fc1.bias"])
         y.w_fc2, y.b_fc2 = k.t(sd[p + "mlp.fc2.weight"]), k.t(sd[p + "mlp.fc2.bias"])
     return layers
 
@@ -240,7 +269,8 @@ class HipClipVisionEncoder:
 
     MAX_BATCH = 64
 
-    def __init__(self, state_dict: Dict[str, torch.Tensor], num_heads: int, device, eps: float = 1e-5):
+    def __init__(self, state_dict: Dict[str, torch.Tensor], num_heads: int, device, eps: float = 1e-5, head_dim: int = 64,
+                 act: str = "quick_gelu"):
         device = torch.device(device)
         if device.type != "cuda":
             raise RFError(f"HipClipVisionEncoder: device {device}; the HIP path has no CPU fallback")
@@ -255,8 +285,7 @@ class HipClipVisionEncoder:
             raise RFError("HipClipVisionEncoder: no vision_model.encoder.layers.* keys in the state dict")
         pw = sd["embeddings.patch_embedding.weight"]                     # [hidden, 3, p, p]
         D, _, P, _ = pw.shape
-        if D != 64 * num_heads:
-            raise RFError(f"HipClipVisionEncoder: hidden {D} with {num_heads} heads: the attention kernel is built for a head dim of 64")
+        self._opts = _tower_opts("HipClipVisionEncoder", D, num_heads, head_dim, act)
         T = sd["embeddings.position_embedding.weight"].shape[0]
         g = int(round(math.sqrt(T - 1)))
         if g * g + 1 != T:
@@ -266,7 +295,7 @@ class HipClipVisionEncoder:
         self.proj_dim = sd["visual_projection.weight"].shape[0]
         k = self._k = _Keep(device)
         f = lambda t: t.detach().float()  # noqa: E731
-        self._layers = _clip_layers(k, sd, n_layers)
+        self._layers = _clip_layers(k, sd, n_layers, head_dim)
         wpad = torch.zeros(D, self.k_pad)
         wpad[:, : 3 * P * P] = f(pw).reshape(D, 3 * P * P).cpu()
         mask = torch.zeros(self.s_pad, self.s_pad, device=device)
@@ -278,7 +307,7 @@ class HipClipVisionEncoder:
         w.patch_w, w.class_embed, w.pos_embed = k.t(wpad), k.t(sd["embeddings.class_embedding"]), k.t(sd["embeddings.position_embedding.weight"])
         w.pre_ln_scale, w.pre_ln_shift = k.t(f(sd["pre_layrnorm.weight"]) - 1.0), k.t(sd["pre_layrnorm.bias"])
         w.post_ln_scale, w.post_ln_shift = k.t(f(sd["post_layernorm.weight"]) - 1.0), k.t(sd["post_layernorm.bias"])
-        w.proj, w.mask = k.t(sd["visual_projection.weight"]), self._mask.data_ptr()
+        w.proj, w.mask = k.t(_kpad(sd["visual_projection.weight"])), self._mask.data_ptr()
         w.layer = C.cast(self._layers, C.POINTER(L.rf_clip_layer))
         self._ws = _Workspace(device)
 
@@ -318,9 +347,10 @@ class HipClipVisionEncoder:
         out = torch.empty(B, self.proj_dim, dtype=BF, device=self.device)
         for b0 in range(0, B, self.MAX_BATCH):
             nb = min(self.MAX_BATCH, B - b0)
-            ws = self._ws.get(lib.rf_clip_vision_workspace_bytes(C.byref(w), nb))
-            L.check(lib.rf_clip_vision_encode(C.byref(w), patches[b0].data_ptr(), nb, out[b0].data_ptr(), C.byref(ws), stream_ptr()),
-                    "rf_clip_vision_encode")
+            o = C.byref(self._opts)
+            ws = self._ws.get(_ws_bytes(lib.rf_clip_vision_workspace_bytes_opts(C.byref(w), o, nb), "rf_clip_vision_workspace_bytes_opts"))
+            L.check(lib.rf_clip_vision_encode_opts(C.byref(w), o, patches[b0].data_ptr(), nb, out[b0].data_ptr(), C.byref(ws), stream_ptr()),
+                    "rf_clip_vision_encode_opts")
         return out
 
 

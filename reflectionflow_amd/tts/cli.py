@@ -55,8 +55,8 @@ def main(mode: str, argv=None):
     pipe = runner.build_pipeline(config, dev, synthetic=args.synthetic, small=args.small)
     os.makedirs(args.output_dir, exist_ok=True)
     kw = {}
-    if mode == "reflection" and config.get("verifier_args", {}).get("name") == "clip":
-        # verifier_args = {"name": "clip", "clip_model_path": DIR}: the on-device CLIP-score verifier (tts/clip_verifier.py)
+    if mode == "reflection" and config.get("verifier_args", {}).get("name") in ("clip", "pickscore"):
+        # verifier_args = {"name": "clip" | "pickscore", "clip_model_path": DIR}: the on-device CLIP-score verifier (tts/clip_verifier.py)
         from .clip_verifier import build_from_config
         v = build_from_config(config, pipe, synthetic=args.synthetic, small=args.small)
         kw = dict(score_batch=v.score_batch, score_images=v.score_images)

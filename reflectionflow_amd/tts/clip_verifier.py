@@ -1,6 +1,7 @@
 """On-device CLIP-score verifier for the reflection search.
 
-The verifier is transformers' `CLIPModel` (clip-vit-large-patch14 layout) applied to what the reference's verifier reads -- the
+The verifier is transformers' `CLIPModel` (clip-vit-large-patch14 layout, or the ViT-H/14 layout of PickScore / HPSv2 / LAION CLIP-H:
+vision head dim 80, `hidden_act = "gelu"`) applied to what the reference's verifier reads -- the
 candidate's saved 8-bit PNG -- and scored against the ORIGINAL prompt, as the reference scores every round
 (tts_reflectionflow.py:157-170, 345-352):
 
@@ -22,7 +23,7 @@ from __future__ import annotations
 import json
 import math
 import os
-from typing import Callable, Dict, List, Sequence
+from typing import Callable, Dict, List, Optional, Sequence
 
 import torch
 
@@ -36,16 +37,30 @@ VIT_L14 = dict(text=dict(vocab=49408, hidden=768, heads=12, inter=3072, layers=1
 # --synthetic --small
 TINY = dict(text=dict(vocab=512, hidden=128, heads=2, inter=256, layers=2, max_pos=77),
             vision=dict(hidden=128, heads=2, inter=256, layers=2, image_size=224, patch=14), projection_dim=64)
+# yuvalkirstain/PickScore_v1, HPSv2, laion/CLIP-ViT-H-14-laion2B-s32B-b79K: one CLIPModel geometry, vision head dim 80, erf GELU
+VIT_H14 = dict(text=dict(vocab=49408, hidden=1024, heads=16, inter=4096, layers=24, max_pos=77),
+               vision=dict(hidden=1280, heads=16, inter=5120, layers=32, image_size=224, patch=14), projection_dim=1024, act="gelu")
+# --synthetic --small with geometry "vit_h14": 2 layers per tower, vision head dim 80, erf GELU
+TINY_H = dict(text=dict(vocab=512, hidden=128, heads=2, inter=256, layers=2, max_pos=77),
+              vision=dict(hidden=160, heads=2, inter=320, layers=2, image_size=224, patch=14), projection_dim=64, act="gelu")
+GEOMETRIES = {"vit_l14": (VIT_L14, TINY), "vit_h14": (VIT_H14, TINY_H)}        # verifier_args.geometry -> (full, --small)
+
+
+def tower_config(cfg: dict) -> dict:
+    """ClipScoreVerifier's `model_config` of a geometry table (VIT_L14, VIT_H14, ...)."""
+    return dict(text_heads=cfg["text"]["heads"], vision_heads=cfg["vision"]["heads"], hidden_act=cfg.get("act", "quick_gelu"))
 
 
 class ClipScoreVerifier:
     """`score_batch(latents [n, S, 64], seeds, prompt) -> (f32 [n], i32 [n])` and `score_images(paths, prompt)` for
     runner.run_reflection_search.  `clip_state_dict`: an HF CLIPModel state dict (`text_model.*`, `vision_model.*`,
     `text_projection.weight`, `visual_projection.weight`, `logit_scale`); `tokenize(prompts) -> ids [B, L]` (CLIP BPE ids, EOS the
-    largest id for the legacy eos_token_id = 2 config); height / width: the candidates' image size."""
+    largest id for the legacy eos_token_id = 2 config); height / width: the candidates' image size.  `model_config`: the head counts
+    and activation of the checkpoint's config.json (`text_heads`, `vision_heads`, `hidden_act`; what `load_clip_dir` returns);
+    None = clip-vit-large-patch14's (head dim 64 on both towers, quick_gelu)."""
 
     def __init__(self, pipe, clip_state_dict: Dict[str, torch.Tensor], tokenize: Callable[[List[str]], torch.Tensor], height: int, width: int,
-                 eos_token_id: int = 2, eps: float = 1e-5):
+                 eos_token_id: int = 2, eps: float = 1e-5, model_config: Optional[dict] = None):
         from ..flux.vae_hip import HipVAE
         if pipe.vae is None:
             raise RFError("ClipScoreVerifier: the pipeline has no VAE -- the verifier scores decoded images (load a pipeline with a vae/ "
@@ -59,8 +74,13 @@ class ClipScoreVerifier:
         vision = {k: v for k, v in sd.items() if k.startswith("vision_model.") or k == "visual_projection.weight"}
         if not text or not vision or "text_projection.weight" not in sd or "logit_scale" not in sd:
             raise RFError("ClipScoreVerifier: needs a CLIPModel state dict (text_model.*, vision_model.*, text/visual_projection, logit_scale)")
-        self.text = HipClipTextEncoder(text, text["embeddings.token_embedding.weight"].shape[1] // 64, dev, eos_token_id=eos_token_id, eps=eps)
-        self.vision = HipClipVisionEncoder(vision, vision["vision_model.embeddings.patch_embedding.weight"].shape[0] // 64, dev, eps=eps)
+        t_hidden, v_hidden = text["embeddings.token_embedding.weight"].shape[1], vision["vision_model.embeddings.patch_embedding.weight"].shape[0]
+        mc = dict(model_config or {})
+        t_heads, v_heads, act = int(mc.get("text_heads", t_hidden // 64)), int(mc.get("vision_heads", v_hidden // 64)), mc.get("hidden_act", "quick_gelu")
+        if t_heads <= 0 or v_heads <= 0 or t_hidden % t_heads or v_hidden % v_heads:
+            raise RFError(f"ClipScoreVerifier: {t_heads} / {v_heads} heads do not divide the hidden widths {t_hidden} / {v_hidden}")
+        self.text = HipClipTextEncoder(text, t_heads, dev, eos_token_id=eos_token_id, eps=eps, head_dim=t_hidden // t_heads, act=act)
+        self.vision = HipClipVisionEncoder(vision, v_heads, dev, eps=eps, head_dim=v_hidden // v_heads, act=act)
         self.text_projection = sd["text_projection.weight"].detach().to(dev, torch.bfloat16).contiguous()
         self.logit_scale = float(sd["logit_scale"].float())
         self._text_cache: Dict[str, torch.Tensor] = {}
@@ -205,34 +225,60 @@ def synthetic_tokenize(vocab: int, length: int = 77) -> Callable[[List[str]], to
     return tokenize
 
 
-def load_clip_dir(path: str):
-    """An HF CLIPModel directory: config.json + model.safetensors + tokenizer files -> (state dict, tokenize, eos_token_id)."""
-    from safetensors.torch import load_file
-    from transformers import CLIPTokenizer
+def read_clip_config(path: str) -> dict:
+    """What the verifier needs of an HF CLIPModel directory's config.json: head counts, activation, layer_norm_eps, projection_dim and
+    the text tower's eos_token_id (49407 in the LAION / PickScore configs: pooling at the first EOS; 2 in OpenAI's legacy configs:
+    pooling at the largest id).  Keys a config leaves out take CLIPConfig's defaults."""
     with open(os.path.join(path, "config.json")) as f:
         cfg = json.load(f)
+    t, v = cfg.get("text_config") or {}, cfg.get("vision_config") or {}
+    t_act, v_act = t.get("hidden_act", "quick_gelu"), v.get("hidden_act", "quick_gelu")
+    if t_act != v_act:
+        raise RFError(f"{path}: text hidden_act {t_act!r} != vision hidden_act {v_act!r}; the verifier runs both towers with one activation")
+    t_eps, v_eps = float(t.get("layer_norm_eps", 1e-5)), float(v.get("layer_norm_eps", 1e-5))
+    if t_eps != v_eps:
+        raise RFError(f"{path}: text layer_norm_eps {t_eps} != vision layer_norm_eps {v_eps}")
+    return dict(text_heads=int(t.get("num_attention_heads", 8)), vision_heads=int(v.get("num_attention_heads", 12)), hidden_act=t_act,
+                layer_norm_eps=t_eps, projection_dim=int(cfg.get("projection_dim", 512)), eos_token_id=int(t.get("eos_token_id", 2)))
+
+
+def load_clip_dir(path: str):
+    """An HF CLIPModel directory: config.json + model.safetensors + tokenizer files -> (state dict, tokenize, model config); the
+    model config is `read_clip_config`'s."""
+    mc = read_clip_config(path)
+    from safetensors.torch import load_file
+    from transformers import CLIPTokenizer
     sd = load_file(os.path.join(path, "model.safetensors"))
+    P = sd["text_projection.weight"].shape[0] if "text_projection.weight" in sd else mc["projection_dim"]
+    if P != mc["projection_dim"]:
+        raise RFError(f"{path}: text_projection has {P} rows, config.json says projection_dim = {mc['projection_dim']}")
     tok = CLIPTokenizer.from_pretrained(path, local_files_only=True)
 
     def tokenize(prompts: List[str]) -> torch.Tensor:
         return tok(list(prompts), padding="max_length", max_length=77, truncation=True, return_tensors="pt")["input_ids"]
-    return sd, tokenize, int(cfg.get("text_config", {}).get("eos_token_id", 2))
+    return sd, tokenize, mc
 
 
 def build_from_config(config: dict, pipe, synthetic: bool = False, small: bool = False) -> ClipScoreVerifier:
-    """The verifier `verifier_args = {"name": "clip", "clip_model_path": DIR}` names; with `synthetic`, a seeded random-init CLIP of
-    ViT-L/14 geometry (TINY with `small`) and the synthetic tokenizer.  Switches the pipeline's VAE to the HIP path."""
+    """The verifier `verifier_args = {"name": "clip" | "pickscore", "clip_model_path": DIR}` names: DIR is an HF CLIPModel directory
+    (clip-vit-large-patch14, or a ViT-H/14 one: PickScore_v1, HPSv2, LAION CLIP-H); its config.json decides heads and activation.
+    "pickscore" is an alias: PickScore's score IS exp(logit_scale) * cos(image, text) behind the CLIP processor, a scalar metric
+    sorted with `scalar_sort_key`.  With `synthetic`: a seeded random-init CLIP of `verifier_args.geometry` ("vit_l14", the default,
+    or "vit_h14"; their 2-layer TINY / TINY_H forms with `small`) and the synthetic tokenizer.  Switches the pipeline's VAE to the HIP path."""
     va, pa = config.get("verifier_args", {}), config["pipeline_args"]
     if pipe.vae is None:
         raise RFError("the CLIP verifier needs a pipeline with a VAE")
     pipe.enable_hip_vae()
     if synthetic:
-        cfg = TINY if small else VIT_L14
+        geo = va.get("geometry", "vit_l14")
+        if geo not in GEOMETRIES:
+            raise RFError(f"verifier_args.geometry {geo!r} (one of {sorted(GEOMETRIES)})")
+        cfg = GEOMETRIES[geo][1 if small else 0]
         seed = int(va.get("seed", 0))
-        sd, tok, eos = synthetic_clip_state(cfg, seed), synthetic_tokenize(cfg["text"]["vocab"]), 2
+        sd, tok, mc = synthetic_clip_state(cfg, seed), synthetic_tokenize(cfg["text"]["vocab"]), dict(tower_config(cfg), eos_token_id=2)
     else:
         if not va.get("clip_model_path"):
-            raise RFError('verifier_args.name == "clip" needs verifier_args.clip_model_path (an HF CLIPModel directory)')
-        sd, tok, eos = load_clip_dir(va["clip_model_path"])
-    return ClipScoreVerifier(pipe, sd, tok, pa["height"], pa["width"], eos_token_id=eos)
-
+            raise RFError(f'verifier_args.name == "{va.get("name", "clip")}" needs verifier_args.clip_model_path (an HF CLIPModel directory)')
+        sd, tok, mc = load_clip_dir(va["clip_model_path"])
+    return ClipScoreVerifier(pipe, sd, tok, pa["height"], pa["width"], eos_token_id=mc["eos_token_id"], eps=mc.get("layer_norm_eps", 1e-5),
+                             model_config=mc)

@@ -55,7 +55,7 @@ def build_pipeline(config: dict, device, synthetic: bool = False, small: bool = 
         cfg = dict(num_layers=2, num_single_layers=2, num_attention_heads=2, joint_attention_dim=256,
                    pooled_projection_dim=64) if small else None
         # the CLIP verifier scores decoded images: a random-init VAE comes with it (the small one: 8x, channels the HIP VAE takes)
-        with_vae = config.get("verifier_args", {}).get("name") == "clip"
+        with_vae = config.get("verifier_args", {}).get("name") in ("clip", "pickscore")
         vcfg = dict(block_out_channels=(64, 64, 128, 128), norm_num_groups=32, mid_block_add_attention=False) if small else None
         pipe = FluxPipeline.synthetic(cfg, seed=0, torch_dtype=dtype, device=device, with_vae=with_vae, vae_config=vcfg)
     else:
@@ -343,6 +343,7 @@ def run_reflection_search(config: dict, prompts: Optional[List[str]], output_dir
     N, R = sa["search_branch"], sa["search_rounds"]
     topk = int(sa.get("topk") or N)                                              # tts_reflectionflow.py:609
     kind = config.get("verifier_args", {}).get("name", "nvila")
+    kind = "clip" if kind == "pickscore" else kind        # an alias (tts/clip_verifier.py): the same scalar metric, the same files
     kind = kind if kind in search.SORT_KEYS else "nvila"
     H, W, csize = pa["height"], pa["width"], pa["condition_size"]
     if hasattr(pipe.vae, "check_geometry"):          # HIP VAE: refuse unsupported sizes before any candidate is generated

@@ -228,7 +228,8 @@ def scalar_sort_key(score: float, label: int, index: int):
 
 
 # "clip": the on-device CLIP-score verifier (tts/clip_verifier.py) -- a scalar metric, sorted like the reference's "openai" branch
-SORT_KEYS = {"nvila": nvila_sort_key, "stub": nvila_sort_key, "openai": scalar_sort_key, "clip": scalar_sort_key}
+# "pickscore": the same verifier on a PickScore checkpoint (a ViT-H/14 CLIPModel)
+SORT_KEYS = {"nvila": nvila_sort_key, "stub": nvila_sort_key, "openai": scalar_sort_key, "clip": scalar_sort_key, "pickscore": scalar_sort_key}
 
 
 def select_topk(scores: Sequence[Tuple[float, int]], topk: int, kind: str = "nvila") -> List[int]:
