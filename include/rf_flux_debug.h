@@ -7,6 +7,7 @@
  *   rf_debug_last_*_path     which kernel form the LAST launch of a family took (read-only)
  *   rf_debug_sk_plan, rf_debug_attn_mix_plan   the host-side work plans (pure arithmetic, callable without a GPU)
  *   rf_debug_clock_probe     the shader clock a probed launch saw (rf_gemm_desc.clock_probe / an open profile)
+ *   rf_debug_text_attention  one launch of the text / CLIP towers' attention kernels on caller buffers (kernel-level parity tests)
  */
 #ifndef RF_FLUX_DEBUG_H
 #define RF_FLUX_DEBUG_H
@@ -61,6 +62,18 @@ int rf_debug_attn_mix_plan(int32_t S, int32_t heads, int32_t num_cus, int32_t* o
 /* which: 0 = the last probed 256x256 GEMM launch, 1 = the last bounded-score attention launch, 2 = the GEMM's epilogue (end of main
  * loop -> stores acknowledged).  mhz = shader clocks per microsecond over workgroup 0's region, us = its duration.  Synchronise first. */
 int rf_debug_clock_probe(int which, double* mhz, double* us);
+/* One launch of the text / CLIP towers' attention (head_dim 64: T5, CLIP-L text, ViT-L; 80: ViT-H/14) on caller buffers, through the
+ * launch code the towers use (same LDS size, grid and instantiation): out = softmax(scale * q.k^T + bias) v per head and sequence, bf16.
+ * B sequences of S tokens, each owning S_pad rows (S_pad % 32 == 0, <= 512 keys at head_dim 64, <= 480 at 80): rows of q [.][ldq],
+ * k [.][ldk] and out [.][ldo] of sequence z start at z * S_pad, head h in columns h * head_dim ...; vt [heads * head_dim][ldvt] is V
+ * transposed (row = channel, column = key) with sequence z's keys at columns z * S_pad.  bias: fp32 [.][S_pad][S_pad] with head stride
+ * bias_hs (0 = shared by the heads); it must hold -inf in the key columns >= S and may be NULL only when S == S_pad.  Rows >= S of out
+ * are not written; rows / keys >= S of q, k, vt must be finite.  qi: 1 | 4 = 64 | 256 queries per workgroup, 0 = the product's rule
+ * (4 when heads * B * ceil(S_pad / 256) >= 256).  Pointers 16-byte aligned, pitches multiples of 8 elements.  Not a switch: it
+ * changes nothing about any other launch. */
+int rf_debug_text_attention(int32_t head_dim, int32_t qi, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
+                            const float* bias, int64_t bias_hs, void* out, int64_t ldo, int32_t heads, int32_t B, int32_t S, int32_t S_pad,
+                            float scale, void* stream);
 
 #ifdef __cplusplus
 }

@@ -273,7 +273,10 @@ _EXTRA_SIGS = {
     "rf_debug_last_attn_path": (C.c_int, []), "rf_debug_last_attn_bwd_path": (C.c_int, []), "rf_debug_last_gemm_path": (C.c_int, []),
                "rf_debug_clock_probe": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
                "rf_debug_sk_plan": (C.c_int, [C.POINTER(rf_gemm_desc), C.c_int32, C.POINTER(C.c_int32)]),
-               "rf_debug_attn_mix_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)])}
+               "rf_debug_attn_mix_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+               # (head_dim, qi, q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, heads, B, S, S_pad, scale, stream)
+               "rf_debug_text_attention": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64,
+                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P])}
 _lib = None
 
 

@@ -436,49 +436,43 @@ int text_gemm(TextCtx& c, const bf16_t* x, int64_t ldx, const void* w, const voi
   return rf_gemm_bf16(&d, c.st);
 }
 
-int text_attention(TextCtx& c, int heads, int inner, const float* bias, int64_t bias_hs, float scale) {
-  const int lds = ta_lds_bytes(c.S_pad);
-  static bool attr = false;
-  if (!attr) {
-    RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn64_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, ta_lds_bytes(TA_MAXS)));
-    RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn64_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, ta_lds_bytes(TA_MAXS)));
-    attr = true;
+// The one launch site of attn64_kernel / attn80_kernel (the towers below and rf_debug_text_attention): LDS size, grid, the dynamic-LDS
+// attribute and the instantiation are decided here and nowhere else.  qi: 1 | 4 = that instantiation, 0 = the product's rule.
+static int text_attention_launch(int head_dim, int qi, const bf16_t* q, int64_t ldq, const bf16_t* k, int64_t ldk, const bf16_t* vt, int64_t ldvt,
+                                 const float* bias, int64_t bias_hs, bf16_t* out, int64_t ldo, int heads, int B, int S, int S_pad, float scale,
+                                 hipStream_t st) {
+  const bool hd80 = head_dim == 80;
+  RF_REQUIRE(S_pad <= (hd80 ? TA80_MAXS : TA_MAXS), RF_ERR_SHAPE, "head-dim-%d attention: S_pad=%d > %d keys (K and V^T stay resident in the 160 KiB LDS)",
+             head_dim, S_pad, hd80 ? TA80_MAXS : TA_MAXS);
+  const int lds = hd80 ? ta80_lds_bytes(S_pad) : ta_lds_bytes(S_pad);
+  static bool attr[2] = {false, false};
+  if (!attr[hd80]) {
+    const int max_lds = hd80 ? ta80_lds_bytes(TA80_MAXS) : ta_lds_bytes(TA_MAXS);
+    RF_CHECK_HIP(hipFuncSetAttribute(hd80 ? (const void*)attn80_kernel<1> : (const void*)attn64_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+    RF_CHECK_HIP(hipFuncSetAttribute(hd80 ? (const void*)attn80_kernel<4> : (const void*)attn64_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+    attr[hd80] = true;
   }
   // a workgroup stages the head's K and V^T (2 x 64 KiB at 512 keys) for its queries: with enough (head, sequence) pairs to fill the
-  // CUs it takes 256 queries instead of 64 and stages a quarter as often
-  const bool wide = (int64_t)heads * c.B * cdiv(c.S_pad, 256) >= 256;
-  ProfScope prof(RF_KC_ATTN, 4.0 * (double)c.S_pad * c.S_pad * 64.0 * heads * c.B, c.st);
-  if (wide)
-    hipLaunchKernelGGL(attn64_kernel<4>, dim3(cdiv(c.S_pad, 256), heads, c.B), dim3(256), lds, c.st, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner,
-                       c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO, (int64_t)inner, c.S, c.S_pad, scale);
-  else
-    hipLaunchKernelGGL(attn64_kernel<1>, dim3(cdiv(c.S_pad, 64), heads, c.B), dim3(256), lds, c.st, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner,
-                       c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO, (int64_t)inner, c.S, c.S_pad, scale);
+  // CUs it takes 256 queries instead of 64 and stages a quarter as often; regroups query tiles only (batch invariance)
+  const bool wide = qi ? qi == 4 : (int64_t)heads * B * cdiv(S_pad, 256) >= 256;
+  ProfScope prof(RF_KC_ATTN, 4.0 * (double)S_pad * S_pad * (double)head_dim * heads * B, st);
+  const dim3 grid(cdiv(S_pad, wide ? 256 : 64), heads, B);
+  auto* const kern = hd80 ? (wide ? attn80_kernel<4> : attn80_kernel<1>) : (wide ? attn64_kernel<4> : attn64_kernel<1>);
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, S, S_pad, scale);
   RF_LAUNCH_CHECK();
   return RF_OK;
 }
 
+// head dim 64: q | k [R][2 * inner], V^T [inner][R], out [R][inner]
+int text_attention(TextCtx& c, int heads, int inner, const float* bias, int64_t bias_hs, float scale) {
+  return text_attention_launch(64, 0, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner, c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO,
+                               (int64_t)inner, heads, c.B, c.S, c.S_pad, scale, c.st);
+}
+
 // head dim 80: q | k [R][2 * inner], V^T [inner][R], out [R][ld_ao] (ld_ao = inner rounded up to the GEMM's K-tile, see clip_layers)
 int text_attention80(TextCtx& c, int heads, int inner, int64_t ld_ao, const float* bias, int64_t bias_hs, float scale) {
-  RF_REQUIRE(c.S_pad <= TA80_MAXS, RF_ERR_SHAPE, "head-dim-80 attention: S_pad=%d > %d keys (K and V^T stay resident in the 160 KiB LDS)", c.S_pad,
-             TA80_MAXS);
-  const int lds = ta80_lds_bytes(c.S_pad);
-  static bool attr = false;
-  if (!attr) {
-    RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn80_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, ta80_lds_bytes(TA80_MAXS)));
-    RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn80_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, ta80_lds_bytes(TA80_MAXS)));
-    attr = true;
-  }
-  const bool wide = (int64_t)heads * c.B * cdiv(c.S_pad, 256) >= 256;   // as text_attention; regroups query tiles only (batch invariance)
-  ProfScope prof(RF_KC_ATTN, 4.0 * (double)c.S_pad * c.S_pad * 80.0 * heads * c.B, c.st);
-  if (wide)
-    hipLaunchKernelGGL(attn80_kernel<4>, dim3(cdiv(c.S_pad, 256), heads, c.B), dim3(256), lds, c.st, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner,
-                       c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO, ld_ao, c.S, c.S_pad, scale);
-  else
-    hipLaunchKernelGGL(attn80_kernel<1>, dim3(cdiv(c.S_pad, 64), heads, c.B), dim3(256), lds, c.st, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner,
-                       c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO, ld_ao, c.S, c.S_pad, scale);
-  RF_LAUNCH_CHECK();
-  return RF_OK;
+  return text_attention_launch(80, 0, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner, c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO, ld_ao,
+                               heads, c.B, c.S, c.S_pad, scale, c.st);
 }
 
 // The pre-LN CLIP encoder layers over the residual stream c.X (B sequences of S_pad rows, width D, MLP width F): shared by the text
@@ -670,4 +664,34 @@ extern "C" int rf_gelu_erf_inplace(void* x, int64_t n, void* stream) {
   hipLaunchKernelGGL(gelu_erf_kernel, dim3(grid_for(n / 8)), dim3(256), 0, st, (bf16_t*)x, n / 8);
   RF_LAUNCH_CHECK();
   return RF_OK;
+}
+
+// One attention launch on caller buffers through the towers' own launch site (tests: parity of attn64_kernel / attn80_kernel at shapes,
+// bias forms and scales no tower reaches).  Operands as documented above attn64_kernel; qi: 1 | 4 = that instantiation, 0 = the
+// product's rule.  Everything is validated before the first HIP call.
+extern "C" int rf_debug_text_attention(int32_t head_dim, int32_t qi, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
+                                       const float* bias, int64_t bias_hs, void* out, int64_t ldo, int32_t heads, int32_t B, int32_t S, int32_t S_pad,
+                                       float scale, void* stream) {
+  const char* who = "rf_debug_text_attention";
+  RF_REQUIRE(head_dim == 64 || head_dim == 80, RF_ERR_UNSUPPORTED, "%s: head_dim=%d (attention kernels exist for 64 and 80)", who, head_dim);
+  RF_REQUIRE(qi == 0 || qi == 1 || qi == 4, RF_ERR_UNSUPPORTED, "%s: qi=%d (instantiations exist for 1 and 4; 0 = the product's rule)", who, qi);
+  const int lim = head_dim == 64 ? TA_MAXS : TA80_MAXS;
+  RF_REQUIRE(S_pad > 0 && S_pad % 32 == 0 && S_pad <= lim, RF_ERR_SHAPE, "%s: S_pad=%d (a multiple of 32, 32 .. %d at head_dim %d)", who, S_pad, lim, head_dim);
+  RF_REQUIRE(S >= 1 && S <= S_pad, RF_ERR_SHAPE, "%s: S=%d (1 .. S_pad = %d)", who, S, S_pad);
+  RF_REQUIRE(B >= 1 && B <= 64, RF_ERR_SHAPE, "%s: B=%d (1 .. 64)", who, B);
+  RF_REQUIRE(heads >= 1 && (int64_t)heads * head_dim <= 4096, RF_ERR_SHAPE, "%s: heads=%d head_dim=%d (need 1 <= heads * head_dim <= 4096)", who, heads, head_dim);
+  RF_REQUIRE(q && k && vt && out, RF_ERR_NULL, "%s: q / k / vt / out NULL", who);
+  RF_REQUIRE(bias || S == S_pad, RF_ERR_NULL, "%s: bias NULL with S=%d < S_pad=%d (padded keys are masked by the bias alone)", who, S, S_pad);
+  RF_REQUIRE(aligned16(q) && aligned16(k) && aligned16(vt) && aligned16(out) && aligned16(bias), RF_ERR_ALIGN, "%s: operand not 16-byte aligned", who);
+  RF_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldvt % 8 == 0 && ldo % 8 == 0 && bias_hs % 4 == 0, RF_ERR_ALIGN,
+             "%s: ldq=%lld ldk=%lld ldvt=%lld ldo=%lld (multiples of 8 elements), bias_hs=%lld (multiple of 4)", who, (long long)ldq, (long long)ldk,
+             (long long)ldvt, (long long)ldo, (long long)bias_hs);
+  const int64_t inner = (int64_t)heads * head_dim;
+  RF_REQUIRE(ldq >= inner && ldk >= inner && ldo >= inner && ldvt >= (int64_t)B * S_pad, RF_ERR_SHAPE,
+             "%s: ldq=%lld ldk=%lld ldo=%lld < heads * head_dim = %lld or ldvt=%lld < B * S_pad = %lld", who, (long long)ldq, (long long)ldk, (long long)ldo,
+             (long long)inner, (long long)ldvt, (long long)B * S_pad);
+  RF_REQUIRE(bias_hs == 0 || bias_hs >= (int64_t)S_pad * S_pad, RF_ERR_SHAPE, "%s: bias_hs=%lld (0 = shared by the heads, else >= S_pad^2 = %lld)", who,
+             (long long)bias_hs, (long long)S_pad * S_pad);
+  return text_attention_launch(head_dim, qi, (const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)vt, ldvt, bias, bias_hs, (bf16_t*)out, ldo, heads, B, S,
+                               S_pad, scale, (hipStream_t)stream);
 }
