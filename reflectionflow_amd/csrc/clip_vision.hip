@@ -203,8 +203,6 @@ static int vision_check(const rf_clip_vision_weights* w, const rf_clip_tower_opt
   return clip_opts_check(o, w->hidden, w->heads, w->mask_S, who);
 }
 
-static const rf_clip_tower_opts CLIP_L_OPTS = {64, RF_CLIP_ACT_QUICK_GELU};
-
 extern "C" int64_t rf_clip_vision_workspace_bytes_opts(const rf_clip_vision_weights* w, const rf_clip_tower_opts* o, int32_t B) {
   const int rc = vision_check(w, o, "rf_clip_vision_workspace_bytes");
   if (rc != RF_OK) return rc;

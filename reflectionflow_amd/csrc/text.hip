@@ -93,26 +93,20 @@ __global__ __launch_bounds__(256) void geglu_rows_kernel(const bf16_t* __restric
   *(u32x4*)(out + (int64_t)row * F + c) = pack8(a);
 }
 
-// CLIP's activation, in place: x * sigmoid(1.702 x)
-__global__ __launch_bounds__(256) void quick_gelu_kernel(bf16_t* __restrict__ x, int64_t n8) {
+// A CLIP tower's MLP activation, in place.  quick_gelu: x * sigmoid(1.702 x).  gelu (transformers' "gelu", the ViT-H towers):
+// x * 0.5 * (1 + erf(x / sqrt(2))) in fp32, one rounding to bf16 -- the operation order of torch.nn.functional.gelu on a bf16 tensor.
+// A row kernel of its own, not a GEMM epilogue: the tower runs once per round, not per step.
+template <int ACT>   // rf_clip_act
+__global__ __launch_bounds__(256) void clip_act_kernel(bf16_t* __restrict__ x, int64_t n8) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= n8) return;
   float a[8];
   unpack8(*(const u32x4*)(x + idx * 8), a);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) a[i] = a[i] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * a[i]));
-  *(u32x4*)(x + idx * 8) = pack8(a);
-}
-
-// transformers' "gelu" (ViT-H towers), in place: x * 0.5 * (1 + erf(x / sqrt(2))) in fp32, one rounding to bf16 -- the operation order of
-// torch.nn.functional.gelu on a bf16 tensor.  A row kernel of its own, not a GEMM epilogue: the tower runs once per round, not per step.
-__global__ __launch_bounds__(256) void gelu_erf_kernel(bf16_t* __restrict__ x, int64_t n8) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= n8) return;
-  float a[8];
-  unpack8(*(const u32x4*)(x + idx * 8), a);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) a[i] = a[i] * 0.5f * (1.0f + erff(a[i] * 0.70710678118654752440f));
+  for (int i = 0; i < 8; ++i) {
+    if constexpr (ACT == RF_CLIP_ACT_GELU) a[i] = a[i] * 0.5f * (1.0f + erff(a[i] * 0.70710678118654752440f));
+    else a[i] = a[i] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * a[i]));
+  }
   *(u32x4*)(x + idx * 8) = pack8(a);
 }
 
@@ -436,14 +430,16 @@ int text_gemm(TextCtx& c, const bf16_t* x, int64_t ldx, const void* w, const voi
   return rf_gemm_bf16(&d, c.st);
 }
 
+int text_attn_max_keys(int head_dim) { return head_dim == 64 ? TA_MAXS : head_dim == 80 ? TA80_MAXS : 0; }   // 0: no kernel for that head dim
+
 // The one launch site of attn64_kernel / attn80_kernel (the towers below and rf_debug_text_attention): LDS size, grid, the dynamic-LDS
 // attribute and the instantiation are decided here and nowhere else.  qi: 1 | 4 = that instantiation, 0 = the product's rule.
 static int text_attention_launch(int head_dim, int qi, const bf16_t* q, int64_t ldq, const bf16_t* k, int64_t ldk, const bf16_t* vt, int64_t ldvt,
                                  const float* bias, int64_t bias_hs, bf16_t* out, int64_t ldo, int heads, int B, int S, int S_pad, float scale,
                                  hipStream_t st) {
   const bool hd80 = head_dim == 80;
-  RF_REQUIRE(S_pad <= (hd80 ? TA80_MAXS : TA_MAXS), RF_ERR_SHAPE, "head-dim-%d attention: S_pad=%d > %d keys (K and V^T stay resident in the 160 KiB LDS)",
-             head_dim, S_pad, hd80 ? TA80_MAXS : TA_MAXS);
+  RF_REQUIRE(S_pad <= text_attn_max_keys(head_dim), RF_ERR_SHAPE, "head-dim-%d attention: S_pad=%d > %d keys (K and V^T stay resident in the 160 KiB LDS)",
+             head_dim, S_pad, text_attn_max_keys(head_dim));
   const int lds = hd80 ? ta80_lds_bytes(S_pad) : ta_lds_bytes(S_pad);
   static bool attr[2] = {false, false};
   if (!attr[hd80]) {
@@ -463,16 +459,19 @@ static int text_attention_launch(int head_dim, int qi, const bf16_t* q, int64_t 
   return RF_OK;
 }
 
-// head dim 64: q | k [R][2 * inner], V^T [inner][R], out [R][inner]
-int text_attention(TextCtx& c, int heads, int inner, const float* bias, int64_t bias_hs, float scale) {
-  return text_attention_launch(64, 0, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner, c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO,
-                               (int64_t)inner, heads, c.B, c.S, c.S_pad, scale, c.st);
+// q | k [R][2 * inner], V^T [inner][R], out [R][ld_ao] (ld_ao = inner, or inner rounded up to the GEMM's K-tile, see clip_layers)
+int text_attention(TextCtx& c, int head_dim, int heads, int inner, int64_t ld_ao, const float* bias, int64_t bias_hs, float scale) {
+  return text_attention_launch(head_dim, 0, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner, c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO,
+                               ld_ao, heads, c.B, c.S, c.S_pad, scale, c.st);
 }
 
-// head dim 80: q | k [R][2 * inner], V^T [inner][R], out [R][ld_ao] (ld_ao = inner rounded up to the GEMM's K-tile, see clip_layers)
-int text_attention80(TextCtx& c, int heads, int inner, int64_t ld_ao, const float* bias, int64_t bias_hs, float scale) {
-  return text_attention_launch(80, 0, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner, c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO, ld_ao,
-                               heads, c.B, c.S, c.S_pad, scale, c.st);
+// A CLIP tower's activation over x[0 .. n) in place, n % 8 == 0
+static int clip_act_inplace(int act, bf16_t* x, int64_t n, hipStream_t st) {
+  ProfScope prof(RF_KC_ROWOP, (double)n * 4, st);
+  auto* const kern = act == RF_CLIP_ACT_GELU ? clip_act_kernel<RF_CLIP_ACT_GELU> : clip_act_kernel<RF_CLIP_ACT_QUICK_GELU>;
+  hipLaunchKernelGGL(kern, dim3(grid_for(n / 8)), dim3(256), 0, st, x, n / 8);
+  RF_LAUNCH_CHECK();
+  return RF_OK;
 }
 
 // The pre-LN CLIP encoder layers over the residual stream c.X (B sequences of S_pad rows, width D, MLP width F): shared by the text
@@ -492,19 +491,11 @@ int clip_layers(TextCtx& c, const rf_clip_layer* layer, int layers, int heads, i
     RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, Dp, R, D, L.ln1_scale, L.ln1_shift, eps, st));
     RF_TRY(text_gemm(c, c.Xn, Dp, L.w_qk, L.b_qk, R, 2 * D, Dp, c.QK, 2 * D, RF_EPI_STORE, nullptr));
     RF_TRY(text_gemm(c, (const bf16_t*)L.w_v, Dp, c.Xn, nullptr, D, R, Dp, c.VT, R, RF_EPI_STORE, nullptr));
-    if (o.head_dim == 64) RF_TRY(text_attention(c, heads, D, mask, 0, 1.0f));
-    else RF_TRY(text_attention80(c, heads, D, Dp, mask, 0, 1.0f));
+    RF_TRY(text_attention(c, o.head_dim, heads, D, Dp, mask, 0, 1.0f));
     RF_TRY(text_gemm(c, c.AO, Dp, L.w_o, L.b_o, R, D, Dp, c.X, D, RF_EPI_STORE, c.X));
     RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, Dp, R, D, L.ln2_scale, L.ln2_shift, eps, st));
     RF_TRY(text_gemm(c, c.Xn, Dp, L.w_fc1, L.b_fc1, R, F, Dp, c.HID, F, RF_EPI_STORE, nullptr));
-    {
-      ProfScope prof(RF_KC_ROWOP, (double)R * F * 4, st);
-      if (o.act == RF_CLIP_ACT_GELU)
-        hipLaunchKernelGGL(gelu_erf_kernel, dim3(grid_for((int64_t)R * F / 8)), dim3(256), 0, st, c.HID, (int64_t)R * F / 8);
-      else
-        hipLaunchKernelGGL(quick_gelu_kernel, dim3(grid_for((int64_t)R * F / 8)), dim3(256), 0, st, c.HID, (int64_t)R * F / 8);
-      RF_LAUNCH_CHECK();
-    }
+    RF_TRY(clip_act_inplace(o.act, c.HID, (int64_t)R * F, st));
     RF_TRY(text_gemm(c, c.HID, F, L.w_fc2, L.b_fc2, R, D, F, c.X, D, RF_EPI_STORE, c.X));
   }
   return RF_OK;
@@ -517,7 +508,7 @@ int clip_opts_check(const rf_clip_tower_opts* o, int hidden, int heads, int S_pa
   RF_REQUIRE(o->act == RF_CLIP_ACT_QUICK_GELU || o->act == RF_CLIP_ACT_GELU, RF_ERR_UNSUPPORTED, "%s: act=%d (0 = quick_gelu, 1 = gelu)", who, o->act);
   RF_REQUIRE(heads > 0 && hidden == heads * o->head_dim && hidden <= 4096, RF_ERR_SHAPE, "%s: hidden=%d heads=%d head_dim=%d (need hidden = heads * head_dim <= 4096)",
              who, hidden, heads, o->head_dim);
-  const int lim = o->head_dim == 64 ? TA_MAXS : TA80_MAXS;
+  const int lim = text_attn_max_keys(o->head_dim);
   RF_REQUIRE(S_pad <= lim, RF_ERR_SHAPE, "%s: S_pad=%d > %d keys, the limit at head_dim %d (K and V^T of a head stay resident in the 160 KiB LDS)", who,
              S_pad, lim, o->head_dim);
   return RF_OK;
@@ -574,7 +565,7 @@ extern "C" int rf_t5_encode(const rf_t5_weights* w, const int32_t* ids, int32_t 
     RF_TRY(rms(L.ln0, c.X, c.Xn));
     RF_TRY(text_gemm(c, c.Xn, D, L.w_qk, nullptr, R, 2 * inner, D, c.QK, 2 * inner, RF_EPI_STORE, nullptr));
     RF_TRY(text_gemm(c, (const bf16_t*)L.w_v, D, c.Xn, nullptr, inner, R, D, c.VT, R, RF_EPI_STORE, nullptr));   // V^T = W_v x^T
-    RF_TRY(text_attention(c, w->heads, inner, w->pos_bias, (int64_t)S_pad * S_pad, 1.0f));                       // T5: no 1/sqrt(d)
+    RF_TRY(text_attention(c, 64, w->heads, inner, inner, w->pos_bias, (int64_t)S_pad * S_pad, 1.0f));                       // T5: no 1/sqrt(d)
     RF_TRY(text_gemm(c, c.AO, inner, L.w_o, nullptr, R, D, inner, c.X, D, RF_EPI_STORE, c.X));
     RF_TRY(rms(L.ln1, c.X, c.Xn));
     RF_TRY(text_gemm(c, c.Xn, D, L.w_wi, nullptr, R, 2 * F, D, c.HID, 2 * F, RF_EPI_STORE, nullptr));
@@ -600,8 +591,6 @@ static int clip_check(const rf_clip_weights* w, const rf_clip_tower_opts* o, int
   RF_REQUIRE(S > 0 && S <= w->max_pos && S <= TA_MAXS, RF_ERR_SHAPE, "%s: S=%d (1 .. min(max_pos = %d, %d))", who, S, w->max_pos, TA_MAXS);
   return clip_opts_check(o, w->hidden, w->heads, (int)round_up(S, 32), who);
 }
-
-static const rf_clip_tower_opts CLIP_L_OPTS = {64, RF_CLIP_ACT_QUICK_GELU};
 
 extern "C" int64_t rf_clip_text_workspace_bytes_opts(const rf_clip_weights* w, const rf_clip_tower_opts* o, int32_t B, int32_t S) {
   const int rc = clip_check(w, o, S, "rf_clip_text_workspace_bytes");
@@ -659,11 +648,7 @@ extern "C" int rf_clip_text_encode(const rf_clip_weights* w, const int32_t* ids,
 extern "C" int rf_gelu_erf_inplace(void* x, int64_t n, void* stream) {
   RF_REQUIRE(x && aligned16(x), RF_ERR_NULL, "rf_gelu_erf_inplace: NULL / unaligned tensor");
   RF_REQUIRE(n > 0 && n % 8 == 0 && n / 8 / 256 < 0x7fffffffll, RF_ERR_SHAPE, "rf_gelu_erf_inplace: n=%lld (a positive multiple of 8)", (long long)n);
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope prof(RF_KC_ROWOP, (double)n * 4, st);
-  hipLaunchKernelGGL(gelu_erf_kernel, dim3(grid_for(n / 8)), dim3(256), 0, st, (bf16_t*)x, n / 8);
-  RF_LAUNCH_CHECK();
-  return RF_OK;
+  return clip_act_inplace(RF_CLIP_ACT_GELU, (bf16_t*)x, n, (hipStream_t)stream);
 }
 
 // One attention launch on caller buffers through the towers' own launch site (tests: parity of attn64_kernel / attn80_kernel at shapes,
@@ -675,7 +660,7 @@ extern "C" int rf_debug_text_attention(int32_t head_dim, int32_t qi, const void*
   const char* who = "rf_debug_text_attention";
   RF_REQUIRE(head_dim == 64 || head_dim == 80, RF_ERR_UNSUPPORTED, "%s: head_dim=%d (attention kernels exist for 64 and 80)", who, head_dim);
   RF_REQUIRE(qi == 0 || qi == 1 || qi == 4, RF_ERR_UNSUPPORTED, "%s: qi=%d (instantiations exist for 1 and 4; 0 = the product's rule)", who, qi);
-  const int lim = head_dim == 64 ? TA_MAXS : TA80_MAXS;
+  const int lim = text_attn_max_keys(head_dim);
   RF_REQUIRE(S_pad > 0 && S_pad % 32 == 0 && S_pad <= lim, RF_ERR_SHAPE, "%s: S_pad=%d (a multiple of 32, 32 .. %d at head_dim %d)", who, S_pad, lim, head_dim);
   RF_REQUIRE(S >= 1 && S <= S_pad, RF_ERR_SHAPE, "%s: S=%d (1 .. S_pad = %d)", who, S, S_pad);
   RF_REQUIRE(B >= 1 && B <= 64, RF_ERR_SHAPE, "%s: B=%d (1 .. 64)", who, B);

@@ -1,4 +1,4 @@
-"""GPU: the ViT-H/14 form of the CLIP-score verifier -- attn80_kernel (head dim 80) and gelu_erf_kernel (csrc/text.hip) through the
+"""GPU: the ViT-H/14 form of the CLIP-score verifier -- attn80_kernel (head dim 80) and clip_act_kernel<RF_CLIP_ACT_GELU> (csrc/text.hip) through the
 *_opts entry points, flux/text_hip.py and tts/clip_verifier.py.
 
 Checker: transformers' CLIPModel in fp32 on the CPU (tests/clip_h_ref.py), hidden_act "gelu", loaded with the bf16-rounded synthetic
@@ -49,7 +49,7 @@ def towers(cfg, seed, dev, eos_token_id=2):
     return sd, venc, tenc
 
 
-# ---- 1. gelu_erf_kernel ----------------------------------------------------------------------------------------------------------
+# ---- 1. clip_act_kernel<RF_CLIP_ACT_GELU> (rf_gelu_erf_inplace) ----------------------------------------------------------------------------------------------------------
 def _ordinal(x):
     """bf16 -> integers in value order (-0 and +0 both 0): |difference| = distance in bf16 ulps"""
     b = x.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
@@ -84,7 +84,7 @@ def test_gelu_erf_kernel_equals_torch_gelu_on_bf16(dev, n):
     assert torch.isfinite(got.float()).all()
     ref_off = _ulp_cap(want, cpu_ref, "torch's device gelu vs the fp32 CPU reference")      # the reference alone meets the cap
     equal = torch.equal(got.view(torch.int16), want.view(torch.int16))
-    hip_off = _ulp_cap(got, cpu_ref, "gelu_erf_kernel vs the fp32 CPU reference")
+    hip_off = _ulp_cap(got, cpu_ref, "clip_act_kernel<GELU> vs the fp32 CPU reference")
     print(f"  n={n}: bit-equal to torch's device gelu: {equal}; vs fp32 CPU reference: hip {hip_off}, torch device {ref_off} elements 1 ulp off")
     if not equal:                                           # torch's device erf differs from erff in the last bit: the cap above decides
         d = int((got.view(torch.int16) != want.view(torch.int16)).sum())
