@@ -522,7 +522,7 @@ int rf_clip_text_encode(const rf_clip_weights* w, const int32_t* ids, int32_t B,
  * ---------------------------------------------------------------------------------- */
 typedef struct rf_clip_vision_weights {
   int32_t layers, hidden, heads, inter;   /* hidden = 64 * heads <= 4096, inter % 64 == 0 */
-  int32_t image_size, patch, proj_dim;    /* tokens T = (image_size / patch)^2 + 1 <= 512; K_pad = round_up(3 patch^2, 64) */
+  int32_t image_size, patch, proj_dim;    /* tokens T = (image_size / patch)^2 + 1 <= 2048 (head dim 80: S_pad <= 480); K_pad = round_up(3 patch^2, 64) */
   int32_t mask_S;                         /* = round_up(T, 32): the mask's size */
   float eps; int32_t _pad;                /* layer_norm_eps (1e-5) */
   const void* patch_w;                    /* patch_embedding.weight as [hidden][K_pad], columns (c, ky, kx), zero beyond 3 patch^2 */
@@ -541,7 +541,7 @@ typedef struct rf_clip_vision_weights {
  * then CLIPImageProcessor: resize the shortest edge to `size` (long edge int(size * long / short)) with antialiased bicubic
  * (a = -0.5, PIL's filter; horizontal pass, rounded and clipped to 8 bits, then vertical pass, as PIL's 8-bit resample), round to
  * 8-bit levels, centre-crop size x size (offset (new - size) / 2, floored), (v / 255 - mean) / std
- * with CLIP's mean / std.  H, W <= 8192, size % patch == 0. */
+ * with CLIP's mean / std.  H, W <= 8192, size <= 512 (224, 336 and 448 are CLIP's processors), size % patch == 0. */
 int rf_clip_preprocess(const void* img, int64_t s_img, int64_t s_row, int64_t s_pix, int64_t s_ch, int32_t B, int32_t H, int32_t W, float a,
                        float b, int32_t size, int32_t patch, void* patches, void* stream);
 int64_t rf_clip_vision_workspace_bytes(const rf_clip_vision_weights* w, int32_t B);
@@ -552,8 +552,10 @@ int rf_clip_vision_encode(const rf_clip_vision_weights* w, const void* patches, 
  * Additive to ABI v17: no struct above changes, the four entry points above ARE the calls below with {64, RF_CLIP_ACT_QUICK_GELU}.
  *   head_dim  64 | 80; hidden == heads * head_dim.  The binding folds 1/sqrt(head_dim) into q_proj (weights and bias).
  *   act       the MLP's activation: quick_gelu, or gelu = x/2 (1 + erf(x / sqrt 2)) in fp32, rounded to bf16 once (F.gelu on bf16).
- * A head's K and V^T stay resident in the LDS: S_pad <= 512 keys at head dim 64, <= 480 at head dim 80 (257 tokens of a 224-px
- * ViT-H/14 need 288); more returns RF_ERR_SHAPE from the size query and the encode call alike.  A hidden width that is no multiple
+ * Keys of one attention call: at head dim 80 a head's K and V^T stay resident in the LDS, S_pad <= 480 (257 tokens of a 224-px
+ * ViT-H/14 need 288); at head dim 64 they stay resident up to S_pad = 512 and are streamed through the LDS in chunks beyond, up to
+ * S_pad = 2048 in the vision tower (ViT-L/14 at 336 px: 577 tokens, S_pad 608); the text tower keeps S <= min(max_pos, 512).  More
+ * returns RF_ERR_SHAPE from the size query and the encode call alike.  A hidden width that is no multiple
  * of the GEMM's 64-element K-tile (test-size towers; 1280 is one): every weight whose K axis is `hidden` (w_qk, w_v, w_o, w_fc1,
  * proj) is passed with row pitch round_up(hidden, 64), zero beyond `hidden`.  Other head dims / activations: RF_ERR_UNSUPPORTED. */
 enum { RF_CLIP_ACT_QUICK_GELU = 0, RF_CLIP_ACT_GELU = 1 };
@@ -566,6 +568,21 @@ int rf_clip_vision_encode_opts(const rf_clip_vision_weights* w, const rf_clip_to
                                const rf_workspace* ws, void* stream);
 /* x[0 .. n) bf16 in place <- gelu (the RF_CLIP_ACT_GELU row kernel on its own); n % 8 == 0, x 16-byte aligned */
 int rf_gelu_erf_inplace(void* x, int64_t n, void* stream);
+/* The towers' head-dim-64 attention as one launch on caller buffers (a binding that runs an encoder of its own around it), through
+ * the towers' launch site: out = softmax(scale * q.k^T + bias) v per head and sequence, bf16.  B sequences of S tokens, each owning
+ * S_pad rows (S_pad % 32 == 0, <= 2048): rows of q [.][ldq], k [.][ldk] and out [.][ldo] of sequence z start at z * S_pad, head h in
+ * columns 64 h ...; vt [64 heads][ldvt] is V transposed (row = channel, column = key) with sequence z's keys at columns z * S_pad.
+ * bias: fp32 [.][S_pad][S_pad] with head stride bias_hs (0 = shared by the heads); it must hold -inf in the key columns >= S and may
+ * be NULL only when S == S_pad.  Rows >= S of out are not written; rows / keys >= S of q, k, vt must be finite.
+ *   head_dim     64; anything else returns RF_ERR_UNSUPPORTED
+ *   qi           1 | 4 = 64 | 256 queries per workgroup, 0 = the towers' rule (4 when heads * B * ceil(S_pad / 256) >= 256)
+ *   stream_keys  0 = the towers' rule: K and V^T resident in the LDS up to S_pad = 512, streamed through it in 128-key chunks with an
+ *                online softmax beyond; 1 = streamed at any S_pad.  A choice of this call alone.
+ * Results are bitwise repeatable and depend on neither B nor qi.  Pointers 16-byte aligned, pitches multiples of 8 elements; every
+ * argument is checked before the first HIP call. */
+int rf_text_attention(int32_t head_dim, int32_t qi, int32_t stream_keys, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt,
+                      int64_t ldvt, const float* bias, int64_t bias_hs, void* out, int64_t ldo, int32_t heads, int32_t B, int32_t S, int32_t S_pad,
+                      float scale, void* stream);
 /* scores[b] = exp(logit_scale) * <img_b / |img_b|, txt / |txt|> in fp32 (img [B][P], txt [P] bf16; logit_scale = the model's
  * log-domain parameter); one workgroup per row, fixed reduction order */
 int rf_clip_score(const void* img, const void* txt, float logit_scale, float* scores, int32_t B, int32_t P, void* stream);

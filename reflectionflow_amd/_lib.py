@@ -234,6 +234,10 @@ _SIGS = {
     "rf_clip_vision_encode_opts": (C.c_int, [C.POINTER(rf_clip_vision_weights), C.POINTER(rf_clip_tower_opts), _P, C.c_int32, _P,
                                              C.POINTER(rf_workspace), _P]),
     "rf_gelu_erf_inplace": (C.c_int, [_P, C.c_int64, _P]),
+    # the towers' head-dim-64 attention on caller buffers; keys beyond 512 (or stream_keys = 1) run the streaming-keys kernel
+    # (head_dim, qi, stream_keys, q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, heads, B, S, S_pad, scale, stream)
+    "rf_text_attention": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64,
+                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
     # round hand-off of the reflection search (csrc/image_handoff.hip)
     "rf_image_levels": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rf_pil_resize_to_vae_input": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32,

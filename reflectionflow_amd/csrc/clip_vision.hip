@@ -3,7 +3,8 @@
 // original prompt.  New here: the image preprocessing (8-bit levels -> CLIPImageProcessor's resize / crop / normalise -> im2col patch
 // rows), the token assembly row kernel and the fused normalise-and-dot score.  The encoder layers are the text tower's
 // (text.hip clip_layers: bf16 MFMA GEMM, attn64_kernel, rf_layernorm_modulate); the attention masks the padded keys (T = 257 tokens
-// of ViT-L/14 at 224 live in S_pad = 288 rows).  rf_clip_tower_opts picks the head dim (64 | 80: attn64_kernel / attn80_kernel) and the
+// of ViT-L/14 at 224 live in S_pad = 288 rows; the 577 tokens of ViT-L/14 at 336 in 608, which text.hip's launch site serves with
+// attn64_stream_kernel: head dim 64 takes up to 2048 keys, head dim 80 up to 480).  rf_clip_tower_opts picks the head dim (64 | 80: attn64_kernel / attn80_kernel) and the
 // activation (quick_gelu | gelu) per call: ViT-H/14 (PickScore, HPSv2, LAION CLIP-H) is hidden 1280 = 16 heads x 80 with erf GELU.
 //
 // Batch invariance.  The search orders candidates by these scores and a rank scores its own candidates in one call, so a row's value
@@ -48,11 +49,17 @@ __device__ __forceinline__ float aa_weight(const AaWin& w, int j) {
 }
 
 constexpr int CP_MAX_SIDE = 8192;   // source rows are staged whole (3 channels fp32) in LDS: 96 KiB at 8192 pixels
+constexpr int CP_MAX_SIZE = 512;    // crop side: a workgroup of 256 threads owns one crop row, a thread NX = 1 (size <= 256) or 2 of its columns
 
 // One workgroup per (crop row y, image): the vertical window's source rows are staged one at a time in LDS as 8-bit levels (fp32),
 // thread x filters its crop column horizontally out of LDS, rounds and clips that to 8 bits (PIL's 8-bit resample keeps the horizontal
 // pass as an 8-bit image; next to saturated edges the clipped overshoot moves the result by up to 7 levels) and accumulates it with
 // the vertical weight; the result is rounded to a level, normalised and scattered to its im2col slot.  Row y = py * patch (ky = 0) also zeroes the K padding of patch row py.
+// NX: crop columns per thread (x = tid + 256 n).  The one structural cap on `size` is this mapping (a crop row = one workgroup, its
+// horizontal windows and accumulators in registers): NX = 1 is the kernel as it always was (size <= 256, same operations in the same
+// order), NX = 2 carries CLIP's 336- and 448-pixel processors, up to CP_MAX_SIZE = 512.  Nothing else depends on size: the LDS holds
+// source rows (<= 8192 pixels) and the tap weights are recomputed per tap, there is no table.
+template <int NX>
 __global__ __launch_bounds__(256) void clip_preprocess_kernel(const bf16_t* __restrict__ img, int64_t s_img, int64_t s_row, int64_t s_pix, int64_t s_ch,
                                                               int H, int W, float a, float b, int newH, int newW, int top, int left, int size,
                                                               int patch, int K_pad, bf16_t* __restrict__ out) {
@@ -64,10 +71,16 @@ __global__ __launch_bounds__(256) void clip_preprocess_kernel(const bf16_t* __re
   const AaWin vy = aa_window(top + y, sy, H);
   const AaWin wx0 = aa_window(left, sx, W), wx1 = aa_window(left + size - 1, sx, W);
   const int sx0 = wx0.lo, span = wx1.lo + wx1.n - sx0;   // windows move right with the output pixel: [sx0, sx0 + span) covers the crop
-  const bool act = tid < size;
-  const AaWin wx = aa_window(left + (act ? tid : 0), sx, W);
+  bool act[NX];
+  AaWin wx[NX];
+  float acc[NX][3];
+#pragma unroll
+  for (int n = 0; n < NX; ++n) {
+    act[n] = tid + 256 * n < size;
+    wx[n] = aa_window(left + (act[n] ? tid + 256 * n : 0), sx, W);
+    acc[n][0] = acc[n][1] = acc[n][2] = 0.0f;
+  }
   const bool ch_fast = s_ch <= s_pix;
-  float acc[3] = {0.0f, 0.0f, 0.0f};
   for (int j = 0; j < vy.n; ++j) {
     const int yy = vy.lo + j;
     __syncthreads();
@@ -80,29 +93,35 @@ __global__ __launch_bounds__(256) void clip_preprocess_kernel(const bf16_t* __re
       row[c * span + p] = rintf(u * 255.0f);                 // the PNG's 8-bit level (numpy's round: half to even)
     }
     __syncthreads();
-    if (act) {
-      const float wy = aa_weight(vy, j);
-      const float* r = row + (wx.lo - sx0);
-      float h[3] = {0.0f, 0.0f, 0.0f};
-      for (int i = 0; i < wx.n; ++i) {
-        const float w = aa_weight(wx, i);
+    const float wy = aa_weight(vy, j);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) h[c] += w * r[c * span + i];
+    for (int n = 0; n < NX; ++n) {
+      if (act[n]) {
+        const float* r = row + (wx[n].lo - sx0);
+        float h[3] = {0.0f, 0.0f, 0.0f};
+        for (int i = 0; i < wx[n].n; ++i) {
+          const float w = aa_weight(wx[n], i);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) h[c] += w * r[c * span + i];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[n][c] += wy * rintf(fminf(fmaxf(h[c], 0.0f), 255.0f));   // PIL's 8-bit intermediate image
       }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) acc[c] += wy * rintf(fminf(fmaxf(h[c], 0.0f), 255.0f));   // PIL's 8-bit intermediate image
     }
   }
   const int gp = size / patch, py = y / patch, ky = y - py * patch, pp = patch * patch;
-  if (act) {
-    const float MEAN[3] = {0.48145466f, 0.4578275f, 0.40821073f}, STD[3] = {0.26862954f, 0.26130258f, 0.27577711f};
-    const int px = tid / patch, kx = tid - px * patch;
-    bf16_t* o = out + ((int64_t)bi * gp * gp + (int64_t)py * gp + px) * K_pad + ky * patch + kx;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float l = rintf(fminf(fmaxf(acc[c], 0.0f), 255.0f));   // 8-bit resize output
-      const float v = l * (1.0f / 255.0f);
-      o[c * pp] = f2bf((v - MEAN[c]) / STD[c]);
+  for (int n = 0; n < NX; ++n) {
+    if (act[n]) {
+      const float MEAN[3] = {0.48145466f, 0.4578275f, 0.40821073f}, STD[3] = {0.26862954f, 0.26130258f, 0.27577711f};
+      const int x = tid + 256 * n, px = x / patch, kx = x - px * patch;
+      bf16_t* o = out + ((int64_t)bi * gp * gp + (int64_t)py * gp + px) * K_pad + ky * patch + kx;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float l = rintf(fminf(fmaxf(acc[n][c], 0.0f), 255.0f));   // 8-bit resize output
+        const float v = l * (1.0f / 255.0f);
+        o[c * pp] = f2bf((v - MEAN[c]) / STD[c]);
+      }
     }
   }
   if (ky == 0) {
@@ -168,8 +187,8 @@ extern "C" int rf_clip_preprocess(const void* img, int64_t s_img, int64_t s_row,
   RF_REQUIRE(img && patches, RF_ERR_NULL, "rf_clip_preprocess: NULL tensor");
   RF_REQUIRE(B > 0 && H > 0 && W > 0 && H <= CP_MAX_SIDE && W <= CP_MAX_SIDE, RF_ERR_SHAPE, "rf_clip_preprocess: B=%d H=%d W=%d (sides 1 .. %d)", B, H,
              W, CP_MAX_SIDE);
-  RF_REQUIRE(size > 0 && size <= 256 && patch > 0 && size % patch == 0, RF_ERR_SHAPE, "rf_clip_preprocess: size=%d patch=%d (size <= 256, %% patch == 0)",
-             size, patch);
+  RF_REQUIRE(size > 0 && size <= CP_MAX_SIZE && patch > 0 && size % patch == 0, RF_ERR_SHAPE, "rf_clip_preprocess: size=%d patch=%d (size <= %d, %% patch == 0)",
+             size, patch, CP_MAX_SIZE);
   RF_REQUIRE(s_row > 0 && s_pix > 0 && s_ch > 0 && (B == 1 || s_img > 0), RF_ERR_SHAPE, "rf_clip_preprocess: strides must be positive");
   // CLIPImageProcessor: shortest edge -> size, long edge int(size * long / short) (transformers' get_resize_output_image_size)
   int newH, newW;
@@ -179,12 +198,14 @@ extern "C" int rf_clip_preprocess(const void* img, int64_t s_img, int64_t s_row,
   const int K_pad = (int)round_up(3 * patch * patch, 64);
   static bool attr = false;
   if (!attr) {
-    RF_CHECK_HIP(hipFuncSetAttribute((const void*)clip_preprocess_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * CP_MAX_SIDE * 4));
+    RF_CHECK_HIP(hipFuncSetAttribute((const void*)clip_preprocess_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * CP_MAX_SIDE * 4));
+    RF_CHECK_HIP(hipFuncSetAttribute((const void*)clip_preprocess_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * CP_MAX_SIDE * 4));
     attr = true;
   }
   hipStream_t st = (hipStream_t)stream;
   ProfScope prof(RF_KC_ROWOP, (double)B * size * size * 3 * 2, st);
-  hipLaunchKernelGGL(clip_preprocess_kernel, dim3(size, B), dim3(256), 3 * W * 4, st, (const bf16_t*)img, s_img, s_row, s_pix, s_ch, H, W, a, b, newH,
+  auto* const kern = size <= 256 ? clip_preprocess_kernel<1> : clip_preprocess_kernel<2>;
+  hipLaunchKernelGGL(kern, dim3(size, B), dim3(256), 3 * W * 4, st, (const bf16_t*)img, s_img, s_row, s_pix, s_ch, H, W, a, b, newH,
                      newW, top, left, size, patch, K_pad, (bf16_t*)patches);
   RF_LAUNCH_CHECK();
   return RF_OK;
@@ -198,7 +219,9 @@ static int vision_check(const rf_clip_vision_weights* w, const rf_clip_tower_opt
              "inter %% 64 == 0, proj_dim %% 8 == 0)", who, w->layers, w->heads, w->hidden, w->inter, w->proj_dim);
   RF_REQUIRE(w->patch > 0 && w->image_size > 0 && w->image_size % w->patch == 0, RF_ERR_SHAPE, "%s: image_size=%d patch=%d", who, w->image_size, w->patch);
   const int g = w->image_size / w->patch, T = g * g + 1;
-  RF_REQUIRE(T <= TA_MAXS, RF_ERR_SHAPE, "%s: %d tokens > %d", who, T, TA_MAXS);
+  // head dim 80: as ever (clip_opts_check below then holds S_pad to the 480 resident keys); head dim 64: the streaming-keys limit
+  const int lim = o && o->head_dim == 80 ? TA_MAXS : text_attn_stream_max_keys(64);
+  RF_REQUIRE(T <= lim, RF_ERR_SHAPE, "%s: %d tokens > %d", who, T, lim);
   RF_REQUIRE(w->mask_S == (int)round_up(T, 32), RF_ERR_SHAPE, "%s: mask is built for S_pad = %d, %d tokens need %d", who, w->mask_S, T, (int)round_up(T, 32));
   return clip_opts_check(o, w->hidden, w->heads, w->mask_S, who);
 }

@@ -12,6 +12,8 @@
 //     in registers, full-row softmax in fp32 (no running maximum: the whole row of scores is in registers), additive fp32 bias
 //     [heads or 1][S_pad][S_pad] (T5: bucketed relative positions; CLIP: the causal mask; both: -inf on padded keys);
 //   * attn80_kernel: the same attention at head dim 80 (the ViT-H/14 towers of PickScore / HPSv2 / LAION CLIP-H), keys <= 480;
+//   * attn64_stream_kernel: head dim 64 with 513 .. 2048 keys (ViT-L/14 at 336 px: 577 tokens): K / V^T chunks of 128 keys double-buffered
+//     through the LDS, online softmax;
 //   * row kernels (HBM-bound, 16-byte accesses): embedding gather (+ position rows), T5 RMS norm, gelu_new(a) * b, quick_gelu, gelu (erf).
 #include "common.hpp"
 #include "text_internal.hpp"
@@ -387,6 +389,201 @@ __global__ __launch_bounds__(256) void attn80_kernel(const bf16_t* __restrict__ 
   }   // it
 }
 
+// ---- attention, head dim 64, keys streamed through the LDS (S_pad <= TAS_MAXS) --------------------------------------------------------
+// attn64_kernel's operand contract word for word (q, k [S_pad][ld], vt [heads * 64][ldvt], bias fp32 [.][S_pad][S_pad] with head stride
+// bias_hs or NULL, out [S][ldo], scale, S_pad % 32 == 0, blockIdx.z = sequence, rows / keys >= S masked by the bias alone, rows >= S
+// not written) for towers with more keys than a CU's LDS holds (ViT-L/14 at 336 px: 577 tokens, S_pad 608).  Decisions:
+//   * Chunks of TAS_CK = 128 keys, two LDS buffers.  A buffer is attn64_kernel's image of a 128-key head: K rows of 128 B with the
+//     16-byte chunk c of row r at c ^ (r & 7), V^T rows of pitch 2 * 128 + 16 B with the key slots of every 32-key block permuted
+//     (slot(key) = 8 (key%16 / 4) + 4 (key / 16) + key % 4); chunk-local rows and blocks, and 128 % 32 == 0, so both formulas are
+//     the resident kernel's with S_pad = 128 (V^T fragment reads stay 2-way under the bank model, as there).
+//   * LDS budget: 2 x (128 * 128 + 64 * 272) = 67,584 B whatever S_pad is: two workgroups per CU (160 KiB / 66 KiB), i.e. two waves
+//     per SIMD, which __launch_bounds__(256, 2) also asks of the register allocator (<= 256 VGPR + AGPR).  256 keys per chunk would
+//     be 133,120 B = one workgroup per CU and twice the score registers for half the barriers; with one barrier per chunk and the
+//     next chunk's loads in flight the barrier is not what this kernel waits for.
+//   * Double buffering: chunk c + 1 is loaded from global memory into registers (4 + 4 x 16 B per thread) BEFORE the MFMAs of chunk
+//     c and written to the other buffer after them; one __syncthreads per chunk (buffer (c + 1) & 1 was last read in iteration
+//     c - 1, which every wave has left).  The last chunk may be partial (a multiple of 32 keys): loads, LDS writes, score tiles and
+//     PV blocks past its keys are skipped by workgroup-uniform tests.
+//   * Online softmax in the exp2 domain, per query: running maximum m and running sum l (each lane keeps the partial sum of its own
+//     keys, reduced over the four lane groups once at the end, as in the resident kernel).  Per chunk: scores of <= 8 tiles in
+//     registers (32 per query tile instead of the resident kernel's 128), chunk maximum over the lane groups, m' = max(m, chunk),
+//     alpha = exp2(m - m'), O and l scaled by alpha in fp32, P = exp2(s - m') rounded to bf16 once for the PV MFMA, l += the
+//     unrounded P.  While a query has seen only -inf (causal rows ahead of their first key, padded rows) the subtrahend is 0, not
+//     -inf: P = exp2(-inf) = 0 and alpha = exp2(-inf - 0) = 0 on a state of zeros.  A chunk of -inf under a finite m gives m' = m,
+//     alpha = exp2(0) = 1 exactly and P = 0: the state is unchanged bit for bit.  1 / l is formed only for rows that are written.
+//   * QI as in attn64_kernel: a workgroup stages every chunk once for 64 * QI queries; the QI tiles of a wave keep separate states
+//     and run the same instructions in the same order as one tile alone, and the multiply-adds that could contract differently are
+//     written as fmaf.  No atomics, fixed order: results are bitwise repeatable and depend on neither B nor QI.
+constexpr int TAS_CK = 128;                        // keys per chunk
+constexpr int TAS_VP = TAS_CK * 2 + 16;            // V^T row pitch of a chunk, bytes
+constexpr int TAS_KB = TAS_CK * 128;               // K image of a chunk, bytes
+constexpr int TAS_BUF = TAS_KB + 64 * TAS_VP;      // one buffer
+constexpr int TAS_LDS = 2 * TAS_BUF;
+static_assert(TAS_CK % 32 == 0 && TAS_CK * 8 == 4 * 256 && 64 * (TAS_CK / 8) == 4 * 256, "a thread stages 4 + 4 16-byte pieces of a chunk");
+static_assert(2 * TAS_LDS <= 160 * 1024, "two workgroups per CU");
+
+// chunk's K rows and V^T columns -> registers; nk: its keys (0: nothing to load)
+__device__ __forceinline__ void tas_fetch(u32x4 (&kr)[4], u32x4 (&vr)[4], const bf16_t* __restrict__ k, int64_t ldk, const bf16_t* __restrict__ vt,
+                                          int64_t ldvt, int head, int key0, int nk, int tid) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int idx = tid + i * 256;
+    const int r = idx >> 3, c = idx & 7;
+    if (r < nk) kr[i] = *(const u32x4*)(k + (int64_t)(key0 + r) * ldk + head * 64 + c * 8);
+    const int d = idx >> 4, m = idx & 15;
+    if (m * 8 < nk) vr[i] = *(const u32x4*)(vt + (int64_t)(head * 64 + d) * ldvt + key0 + m * 8);
+  }
+}
+
+// registers -> one LDS buffer, in attn64_kernel's images
+__device__ __forceinline__ void tas_stash(const u32x4 (&kr)[4], const u32x4 (&vr)[4], char* buf, int nk, int tid) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int idx = tid + i * 256;
+    const int r = idx >> 3, c = idx & 7;
+    if (r < nk) *(u32x4*)(buf + r * 128 + ((c ^ (r & 7)) << 4)) = kr[i];
+    const int d = idx >> 4, m = idx & 15;
+    if (m * 8 < nk) {
+      const int blk = (m * 8) >> 5, kap = (m * 8) & 31;
+      const int tile = kap >> 4, g0 = (kap & 15) >> 2;
+      char* dst = buf + TAS_KB + d * TAS_VP + blk * 64;
+      u32x2 lo, hi;
+      lo[0] = vr[i][0]; lo[1] = vr[i][1]; hi[0] = vr[i][2]; hi[1] = vr[i][3];
+      *(u32x2*)(dst + (8 * g0 + 4 * tile) * 2) = lo;
+      *(u32x2*)(dst + (8 * (g0 + 1) + 4 * tile) * 2) = hi;
+    }
+  }
+}
+
+template <int QI>   // query tiles per wave, as attn64_kernel
+__global__ __launch_bounds__(256, 2) void attn64_stream_kernel(const bf16_t* __restrict__ q, int64_t ldq, const bf16_t* __restrict__ k, int64_t ldk,
+                                                               const bf16_t* __restrict__ vt, int64_t ldvt, const float* __restrict__ bias,
+                                                               int64_t bias_hs, bf16_t* __restrict__ out, int64_t ldo, int S, int S_pad, float scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int l15 = lane & 15, g = lane >> 4;
+  const int head = blockIdx.y, qb = blockIdx.x;
+  {
+    const int64_t r0 = (int64_t)blockIdx.z * S_pad;
+    q += r0 * ldq; k += r0 * ldk; vt += r0; out += r0 * ldo;
+  }
+  const float NINF = -__builtin_huge_valf();
+  const float LOG2E = 1.4426950408889634f;
+  const float sl2 = scale * LOG2E;
+  // ---- per query tile: Q fragments, bias row, softmax state -----------------------------------------------------------------------
+  bf16x8 qf[QI][2];
+  const float* brow[QI];
+  float mrun[QI], lrun[QI];
+  f32x4 oacc[QI][4];
+#pragma unroll
+  for (int it = 0; it < QI; ++it) {
+    const int q_row = (qb * QI + it) * 64 + w * 16 + l15;
+    const int q_ld = q_row < S_pad ? q_row : S_pad - 1;
+#pragma unroll
+    for (int ds = 0; ds < 2; ++ds) qf[it][ds] = *(const bf16x8*)(q + (int64_t)q_ld * ldq + head * 64 + ds * 32 + g * 8);
+    brow[it] = bias ? bias + head * bias_hs + (int64_t)q_ld * S_pad + 4 * g : nullptr;
+    mrun[it] = NINF;
+    lrun[it] = 0.f;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) oacc[it][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  // ---- chunk 0 -> buffer 0 -----------------------------------------------------------------------------------------------------------
+  const int nch = (S_pad + TAS_CK - 1) / TAS_CK;
+  u32x4 kr[4], vr[4];
+  tas_fetch(kr, vr, k, ldk, vt, ldvt, head, 0, min(TAS_CK, S_pad), tid);
+  tas_stash(kr, vr, smem, min(TAS_CK, S_pad), tid);
+  __syncthreads();
+#pragma unroll 1
+  for (int c = 0; c < nch; ++c) {
+    const int key0 = c * TAS_CK, nk = min(TAS_CK, S_pad - key0);
+    const int nk_next = c + 1 < nch ? min(TAS_CK, S_pad - key0 - TAS_CK) : 0;
+    tas_fetch(kr, vr, k, ldk, vt, ldvt, head, key0 + TAS_CK, nk_next, tid);   // in flight under this chunk's MFMAs
+    const char* const kl = smem + (c & 1) * TAS_BUF;
+    const char* const vl = kl + TAS_KB;
+    const int nt = nk >> 4;
+#pragma unroll
+    for (int it = 0; it < QI; ++it) {
+      if ((qb * QI + it) * 64 < S_pad) {
+        // scores: S^T tile t = K[key0 + 16t ..] Q^T: this lane holds keys key0 + 16t + 4g + r of query l15
+        f32x4 s[TAS_CK / 16];
+        float cm = NINF;
+#pragma unroll
+        for (int t = 0; t < TAS_CK / 16; ++t) {
+          if (t < nt) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            const int r = t * 16 + l15;
+#pragma unroll
+            for (int ds = 0; ds < 2; ++ds) {
+              const bf16x8 kf = *(const bf16x8*)(kl + r * 128 + (((ds * 4 + g) ^ (r & 7)) << 4));
+              acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[it][ds], acc, 0, 0, 0);
+            }
+            f32x4 b = {0.f, 0.f, 0.f, 0.f};
+            if (brow[it]) b = *(const f32x4*)(brow[it] + key0 + t * 16);
+#pragma unroll
+            for (int r2 = 0; r2 < 4; ++r2) {
+              acc[r2] = __builtin_fmaf(acc[r2], sl2, b[r2] * LOG2E);
+              cm = fmaxf(cm, acc[r2]);
+            }
+            s[t] = acc;
+          }
+        }
+        cm = fmaxf(cm, __shfl_xor(cm, 16));
+        cm = fmaxf(cm, __shfl_xor(cm, 32));
+        const float mnew = fmaxf(mrun[it], cm);
+        const float msub = mnew > NINF ? mnew : 0.f;               // only -inf so far: keep the arithmetic finite
+        const float alpha = __builtin_amdgcn_exp2f(mrun[it] - msub);   // -inf - finite: 0; m unchanged: exp2(0) = 1
+        mrun[it] = mnew;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+          for (int r2 = 0; r2 < 4; ++r2) oacc[it][dt][r2] *= alpha;
+        float ls = 0.f;
+#pragma unroll
+        for (int b = 0; b < TAS_CK / 32; ++b) {
+          if (2 * b < nt) {
+            float p[8];
+#pragma unroll
+            for (int r2 = 0; r2 < 4; ++r2) {
+              p[r2] = __builtin_amdgcn_exp2f(s[2 * b][r2] - msub);
+              p[4 + r2] = __builtin_amdgcn_exp2f(s[2 * b + 1][r2] - msub);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) ls += p[i];
+            const bf16x8 pf = __builtin_bit_cast(bf16x8, pack8(p));
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+              const bf16x8 vf = *(const bf16x8*)(vl + (dt * 16 + l15) * TAS_VP + b * 64 + g * 16);
+              oacc[it][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, oacc[it][dt], 0, 0, 0);
+            }
+          }
+        }
+        lrun[it] = __builtin_fmaf(lrun[it], alpha, ls);
+      }
+    }
+    tas_stash(kr, vr, smem + ((c + 1) & 1) * TAS_BUF, nk_next, tid);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int it = 0; it < QI; ++it) {
+    const int q_row = (qb * QI + it) * 64 + w * 16 + l15;
+    float l = lrun[it];
+    l += __shfl_xor(l, 16);
+    l += __shfl_xor(l, 32);
+    if (q_row < S) {
+      const float inv = 1.0f / l;
+      bf16_t* orow = out + (int64_t)q_row * ldo + head * 64 + 4 * g;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        u32x2 v;
+        v[0] = pack2(oacc[it][dt][0] * inv, oacc[it][dt][1] * inv);
+        v[1] = pack2(oacc[it][dt][2] * inv, oacc[it][dt][3] * inv);
+        *(u32x2*)(orow + dt * 16) = v;
+      }
+    }
+  }
+}
+
 // ---- host side (TextCtx / TextSizes: text_internal.hpp) ------------------------------------------------------------------------
 int text_ctx(TextCtx& c, const TextSizes& z, int B, int S, int S_pad, const rf_workspace* ws, hipStream_t st, const char* who) {
   RF_REQUIRE(ws && ws->base && aligned16(ws->base) && ws->bytes >= z.total, RF_ERR_WORKSPACE, "%s: workspace %lld < required %lld bytes", who,
@@ -431,13 +628,35 @@ int text_gemm(TextCtx& c, const bf16_t* x, int64_t ldx, const void* w, const voi
 }
 
 int text_attn_max_keys(int head_dim) { return head_dim == 64 ? TA_MAXS : head_dim == 80 ? TA80_MAXS : 0; }   // 0: no kernel for that head dim
+int text_attn_stream_max_keys(int head_dim) { return head_dim == 64 ? TAS_MAXS : 0; }                      // 0: no streaming kernel
 
-// The one launch site of attn64_kernel / attn80_kernel (the towers below and rf_debug_text_attention): LDS size, grid, the dynamic-LDS
-// attribute and the instantiation are decided here and nowhere else.  qi: 1 | 4 = that instantiation, 0 = the product's rule.
-static int text_attention_launch(int head_dim, int qi, const bf16_t* q, int64_t ldq, const bf16_t* k, int64_t ldk, const bf16_t* vt, int64_t ldvt,
-                                 const float* bias, int64_t bias_hs, bf16_t* out, int64_t ldo, int heads, int B, int S, int S_pad, float scale,
-                                 hipStream_t st) {
+// The one launch site of attn64_kernel / attn80_kernel / attn64_stream_kernel (the towers below, rf_text_attention and
+// rf_debug_text_attention): the kernel, LDS size, grid, the dynamic-LDS attribute and the instantiation are decided here and nowhere
+// else.  qi: 1 | 4 = that instantiation, 0 = the product's rule.  stream_keys: 0 = the product's rule (the resident kernel up to its key
+// limit, at head dim 64 the streaming kernel beyond), 1 = the streaming kernel at any S_pad (head dim 64).
+static int text_attention_launch(int head_dim, int qi, int stream_keys, const bf16_t* q, int64_t ldq, const bf16_t* k, int64_t ldk, const bf16_t* vt,
+                                 int64_t ldvt, const float* bias, int64_t bias_hs, bf16_t* out, int64_t ldo, int heads, int B, int S, int S_pad,
+                                 float scale, hipStream_t st) {
   const bool hd80 = head_dim == 80;
+  // a workgroup stages the head's K and V^T (2 x 64 KiB at 512 keys) for its queries: with enough (head, sequence) pairs to fill the
+  // CUs it takes 256 queries instead of 64 and stages a quarter as often; regroups query tiles only (batch invariance)
+  const bool wide = qi ? qi == 4 : (int64_t)heads * B * cdiv(S_pad, 256) >= 256;
+  const dim3 grid(cdiv(S_pad, wide ? 256 : 64), heads, B);
+  if (stream_keys || (head_dim == 64 && S_pad > TA_MAXS)) {
+    RF_REQUIRE(head_dim == 64, RF_ERR_UNSUPPORTED, "head-dim-%d attention: the streaming-keys kernel exists for head dim 64 only", head_dim);
+    RF_REQUIRE(S_pad <= TAS_MAXS, RF_ERR_SHAPE, "head-dim-64 attention: S_pad=%d > %d keys, the limit of the streaming-keys kernel", S_pad, TAS_MAXS);
+    static bool sattr = false;
+    if (!sattr) {
+      RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn64_stream_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, TAS_LDS));
+      RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn64_stream_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, TAS_LDS));
+      sattr = true;
+    }
+    ProfScope prof(RF_KC_ATTN, 4.0 * (double)S_pad * S_pad * (double)head_dim * heads * B, st);
+    auto* const skern = wide ? attn64_stream_kernel<4> : attn64_stream_kernel<1>;
+    hipLaunchKernelGGL(skern, grid, dim3(256), TAS_LDS, st, q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, S, S_pad, scale);
+    RF_LAUNCH_CHECK();
+    return RF_OK;
+  }
   RF_REQUIRE(S_pad <= text_attn_max_keys(head_dim), RF_ERR_SHAPE, "head-dim-%d attention: S_pad=%d > %d keys (K and V^T stay resident in the 160 KiB LDS)",
              head_dim, S_pad, text_attn_max_keys(head_dim));
   const int lds = hd80 ? ta80_lds_bytes(S_pad) : ta_lds_bytes(S_pad);
@@ -448,11 +667,7 @@ static int text_attention_launch(int head_dim, int qi, const bf16_t* q, int64_t 
     RF_CHECK_HIP(hipFuncSetAttribute(hd80 ? (const void*)attn80_kernel<4> : (const void*)attn64_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
     attr[hd80] = true;
   }
-  // a workgroup stages the head's K and V^T (2 x 64 KiB at 512 keys) for its queries: with enough (head, sequence) pairs to fill the
-  // CUs it takes 256 queries instead of 64 and stages a quarter as often; regroups query tiles only (batch invariance)
-  const bool wide = qi ? qi == 4 : (int64_t)heads * B * cdiv(S_pad, 256) >= 256;
   ProfScope prof(RF_KC_ATTN, 4.0 * (double)S_pad * S_pad * (double)head_dim * heads * B, st);
-  const dim3 grid(cdiv(S_pad, wide ? 256 : 64), heads, B);
   auto* const kern = hd80 ? (wide ? attn80_kernel<4> : attn80_kernel<1>) : (wide ? attn64_kernel<4> : attn64_kernel<1>);
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, S, S_pad, scale);
   RF_LAUNCH_CHECK();
@@ -461,7 +676,7 @@ static int text_attention_launch(int head_dim, int qi, const bf16_t* q, int64_t 
 
 // q | k [R][2 * inner], V^T [inner][R], out [R][ld_ao] (ld_ao = inner, or inner rounded up to the GEMM's K-tile, see clip_layers)
 int text_attention(TextCtx& c, int head_dim, int heads, int inner, int64_t ld_ao, const float* bias, int64_t bias_hs, float scale) {
-  return text_attention_launch(head_dim, 0, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner, c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO,
+  return text_attention_launch(head_dim, 0, 0, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner, c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO,
                                ld_ao, heads, c.B, c.S, c.S_pad, scale, c.st);
 }
 
@@ -508,6 +723,11 @@ int clip_opts_check(const rf_clip_tower_opts* o, int hidden, int heads, int S_pa
   RF_REQUIRE(o->act == RF_CLIP_ACT_QUICK_GELU || o->act == RF_CLIP_ACT_GELU, RF_ERR_UNSUPPORTED, "%s: act=%d (0 = quick_gelu, 1 = gelu)", who, o->act);
   RF_REQUIRE(heads > 0 && hidden == heads * o->head_dim && hidden <= 4096, RF_ERR_SHAPE, "%s: hidden=%d heads=%d head_dim=%d (need hidden = heads * head_dim <= 4096)",
              who, hidden, heads, o->head_dim);
+  if (o->head_dim == 64) {   // beyond the resident kernel's keys the launch site streams them
+    RF_REQUIRE(S_pad <= text_attn_stream_max_keys(64), RF_ERR_SHAPE, "%s: S_pad=%d > %d keys, the limit of the streaming-keys attention at head_dim 64", who,
+               S_pad, text_attn_stream_max_keys(64));
+    return RF_OK;
+  }
   const int lim = text_attn_max_keys(o->head_dim);
   RF_REQUIRE(S_pad <= lim, RF_ERR_SHAPE, "%s: S_pad=%d > %d keys, the limit at head_dim %d (K and V^T of a head stay resident in the 160 KiB LDS)", who,
              S_pad, lim, o->head_dim);
@@ -651,16 +871,11 @@ extern "C" int rf_gelu_erf_inplace(void* x, int64_t n, void* stream) {
   return clip_act_inplace(RF_CLIP_ACT_GELU, (bf16_t*)x, n, (hipStream_t)stream);
 }
 
-// One attention launch on caller buffers through the towers' own launch site (tests: parity of attn64_kernel / attn80_kernel at shapes,
-// bias forms and scales no tower reaches).  Operands as documented above attn64_kernel; qi: 1 | 4 = that instantiation, 0 = the
-// product's rule.  Everything is validated before the first HIP call.
-extern "C" int rf_debug_text_attention(int32_t head_dim, int32_t qi, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
-                                       const float* bias, int64_t bias_hs, void* out, int64_t ldo, int32_t heads, int32_t B, int32_t S, int32_t S_pad,
-                                       float scale, void* stream) {
-  const char* who = "rf_debug_text_attention";
-  RF_REQUIRE(head_dim == 64 || head_dim == 80, RF_ERR_UNSUPPORTED, "%s: head_dim=%d (attention kernels exist for 64 and 80)", who, head_dim);
-  RF_REQUIRE(qi == 0 || qi == 1 || qi == 4, RF_ERR_UNSUPPORTED, "%s: qi=%d (instantiations exist for 1 and 4; 0 = the product's rule)", who, qi);
-  const int lim = text_attn_max_keys(head_dim);
+// The argument checks of the two entry points below, before any HIP call: head_dim / qi are the caller's to check (their sets differ),
+// lim = the most keys that entry point launches at this head dim.
+static int text_attention_args_check(const char* who, int32_t head_dim, int lim, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt,
+                                     int64_t ldvt, const float* bias, int64_t bias_hs, const void* out, int64_t ldo, int32_t heads, int32_t B, int32_t S,
+                                     int32_t S_pad) {
   RF_REQUIRE(S_pad > 0 && S_pad % 32 == 0 && S_pad <= lim, RF_ERR_SHAPE, "%s: S_pad=%d (a multiple of 32, 32 .. %d at head_dim %d)", who, S_pad, lim, head_dim);
   RF_REQUIRE(S >= 1 && S <= S_pad, RF_ERR_SHAPE, "%s: S=%d (1 .. S_pad = %d)", who, S, S_pad);
   RF_REQUIRE(B >= 1 && B <= 64, RF_ERR_SHAPE, "%s: B=%d (1 .. 64)", who, B);
@@ -677,6 +892,35 @@ extern "C" int rf_debug_text_attention(int32_t head_dim, int32_t qi, const void*
              (long long)inner, (long long)ldvt, (long long)B * S_pad);
   RF_REQUIRE(bias_hs == 0 || bias_hs >= (int64_t)S_pad * S_pad, RF_ERR_SHAPE, "%s: bias_hs=%lld (0 = shared by the heads, else >= S_pad^2 = %lld)", who,
              (long long)bias_hs, (long long)S_pad * S_pad);
-  return text_attention_launch(head_dim, qi, (const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)vt, ldvt, bias, bias_hs, (bf16_t*)out, ldo, heads, B, S,
-                               S_pad, scale, (hipStream_t)stream);
+  return RF_OK;
+}
+
+// One attention launch on caller buffers through the towers' own launch site (tests: parity of attn64_kernel / attn80_kernel at shapes,
+// bias forms and scales no tower reaches).  Operands as documented above attn64_kernel; qi: 1 | 4 = that instantiation, 0 = the
+// product's rule.  Everything is validated before the first HIP call.
+extern "C" int rf_debug_text_attention(int32_t head_dim, int32_t qi, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
+                                       const float* bias, int64_t bias_hs, void* out, int64_t ldo, int32_t heads, int32_t B, int32_t S, int32_t S_pad,
+                                       float scale, void* stream) {
+  const char* who = "rf_debug_text_attention";
+  RF_REQUIRE(head_dim == 64 || head_dim == 80, RF_ERR_UNSUPPORTED, "%s: head_dim=%d (attention kernels exist for 64 and 80)", who, head_dim);
+  RF_REQUIRE(qi == 0 || qi == 1 || qi == 4, RF_ERR_UNSUPPORTED, "%s: qi=%d (instantiations exist for 1 and 4; 0 = the product's rule)", who, qi);
+  RF_TRY(text_attention_args_check(who, head_dim, text_attn_max_keys(head_dim), q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, heads, B, S, S_pad));
+  return text_attention_launch(head_dim, qi, 0, (const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)vt, ldvt, bias, bias_hs, (bf16_t*)out, ldo, heads, B,
+                               S, S_pad, scale, (hipStream_t)stream);
+}
+
+// The head-dim-64 attention of the towers as a product call on caller buffers (a binding that runs its own encoder around it), through
+// the same launch site: resident keys up to 512, streamed keys up to 2048.  stream_keys = 1 runs the streaming kernel at any S_pad (a
+// per-call choice, nothing process-wide).  Everything is validated before the first HIP call, by the debug entry's checks.
+extern "C" int rf_text_attention(int32_t head_dim, int32_t qi, int32_t stream_keys, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt,
+                                 int64_t ldvt, const float* bias, int64_t bias_hs, void* out, int64_t ldo, int32_t heads, int32_t B, int32_t S, int32_t S_pad,
+                                 float scale, void* stream) {
+  const char* who = "rf_text_attention";
+  RF_REQUIRE(head_dim == 64, RF_ERR_UNSUPPORTED, "%s: head_dim=%d (head dim 64 only; the streaming-keys kernel has no other)", who, head_dim);
+  RF_REQUIRE(qi == 0 || qi == 1 || qi == 4, RF_ERR_UNSUPPORTED, "%s: qi=%d (instantiations exist for 1 and 4; 0 = the product's rule)", who, qi);
+  RF_REQUIRE(stream_keys == 0 || stream_keys == 1, RF_ERR_UNSUPPORTED, "%s: stream_keys=%d (0 = resident up to %d keys and streamed beyond, 1 = streamed)", who,
+             stream_keys, TA_MAXS);
+  RF_TRY(text_attention_args_check(who, head_dim, text_attn_stream_max_keys(head_dim), q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, heads, B, S, S_pad));
+  return text_attention_launch(head_dim, qi, stream_keys, (const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)vt, ldvt, bias, bias_hs, (bf16_t*)out, ldo,
+                               heads, B, S, S_pad, scale, (hipStream_t)stream);
 }

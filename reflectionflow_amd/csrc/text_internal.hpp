@@ -16,6 +16,7 @@ namespace rf {
 
 constexpr int TA_MAXS = 512;     // keys of attn64_kernel
 constexpr int TA80_MAXS = 480;   // keys of attn80_kernel (text.hip: K + V^T of a head at head dim 80 within the 160 KiB LDS)
+constexpr int TAS_MAXS = 2048;   // keys of attn64_stream_kernel (head dim 64 beyond TA_MAXS): 448 px / 14 needs 1056; a shared fp32 mask of 2048^2 is 16 MiB
 constexpr rf_clip_tower_opts CLIP_L_OPTS = {64, RF_CLIP_ACT_QUICK_GELU};   // the towers of clip-vit-large-patch14: the entry points without opts
 
 struct TextCtx {
@@ -44,7 +45,8 @@ inline TextSizes text_sizes(int rows, int D, int inner, int F, int hid_cols) {  
 int text_ctx(TextCtx& c, const TextSizes& z, int B, int S, int S_pad, const rf_workspace* ws, hipStream_t st, const char* who);
 int text_gemm(TextCtx& c, const bf16_t* x, int64_t ldx, const void* w, const void* b, int M, int N, int K, bf16_t* y, int64_t ldy, int epi,
               const bf16_t* residual);
-int text_attn_max_keys(int head_dim);   // TA_MAXS | TA80_MAXS; 0 for a head dim without a kernel
+int text_attn_max_keys(int head_dim);          // the resident kernels: TA_MAXS | TA80_MAXS; 0 for a head dim without a kernel
+int text_attn_stream_max_keys(int head_dim);   // the streaming-keys kernel: TAS_MAXS at head dim 64, 0 elsewhere
 int text_attention(TextCtx& c, int head_dim, int heads, int inner, int64_t ld_ao, const float* bias, int64_t bias_hs, float scale);
 int clip_layers(TextCtx& c, const rf_clip_layer* layer, int layers, int heads, int D, int F, const float* mask, float eps, const char* who,
                 const rf_clip_tower_opts& o);

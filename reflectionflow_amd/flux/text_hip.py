@@ -265,12 +265,13 @@ class HipClipVisionEncoder:
     """CLIPVisionModel + visual_projection of a Hugging Face `CLIPModel` state dict (`vision_model.*`, `visual_projection.weight`; the
     prefix may be absent): images -> image_embeds [B, projection_dim] bf16 (rf_clip_preprocess + rf_clip_vision_encode).
     Same weight repacking as HipClipTextEncoder; the conv patch embedding becomes a [hidden, K_pad] GEMM weight (columns (c, ky, kx),
-    zero-padded to a multiple of 64)."""
+    zero-padded to a multiple of 64).  `image_size`: the checkpoint's `vision_config.image_size` (224, 336, ...), the size the images
+    are preprocessed at; it must agree with the position-embedding rows ((image_size / patch)^2 + 1).  None: taken from those rows."""
 
     MAX_BATCH = 64
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], num_heads: int, device, eps: float = 1e-5, head_dim: int = 64,
-                 act: str = "quick_gelu"):
+                 act: str = "quick_gelu", image_size: Optional[int] = None):
         device = torch.device(device)
         if device.type != "cuda":
             raise RFError(f"HipClipVisionEncoder: device {device}; the HIP path has no CPU fallback")
@@ -290,6 +291,9 @@ class HipClipVisionEncoder:
         g = int(round(math.sqrt(T - 1)))
         if g * g + 1 != T:
             raise RFError(f"HipClipVisionEncoder: {T} positions is not a square grid + class token")
+        if image_size is not None and int(image_size) != g * P:
+            raise RFError(f"HipClipVisionEncoder: image_size {image_size} with patch {P} needs {(int(image_size) // P) ** 2 + 1} position rows, "
+                          f"the state dict has {T} (a {g * P}-pixel tower)")
         self.device, self.heads, self.hidden, self.patch, self.image_size = device, num_heads, D, P, g * P
         self.tokens, self.s_pad, self.k_pad = T, _pad32(T), (3 * P * P + 63) // 64 * 64
         self.proj_dim = sd["visual_projection.weight"].shape[0]

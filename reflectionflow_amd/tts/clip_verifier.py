@@ -44,6 +44,25 @@ VIT_H14 = dict(text=dict(vocab=49408, hidden=1024, heads=16, inter=4096, layers=
 TINY_H = dict(text=dict(vocab=512, hidden=128, heads=2, inter=256, layers=2, max_pos=77),
               vision=dict(hidden=160, heads=2, inter=320, layers=2, image_size=224, patch=14), projection_dim=64, act="gelu")
 GEOMETRIES = {"vit_l14": (VIT_L14, TINY), "vit_h14": (VIT_H14, TINY_H)}        # verifier_args.geometry -> (full, --small)
+# openai/clip-vit-large-patch14-336: ViT-L/14 at 336 px, 24 x 24 + 1 = 577 tokens (S_pad 608: the streaming-keys attention kernel)
+VIT_L14_336 = dict(text=VIT_L14["text"], vision=dict(VIT_L14["vision"], image_size=336), projection_dim=768)
+# --synthetic --small with geometry "vit_l14_336": 2 layers per tower, 577 vision tokens
+TINY_336 = dict(text=TINY["text"], vision=dict(TINY["vision"], image_size=336), projection_dim=64)
+# the geometries whose vision tower has more keys than the LDS holds (a table of its own: GEOMETRIES is the resident-keys set)
+GEOMETRIES_STREAMED = {"vit_l14_336": (VIT_L14_336, TINY_336)}
+
+
+def geometry_names() -> List[str]:
+    """every value verifier_args.geometry / tools' --geometry takes"""
+    return sorted({**GEOMETRIES, **GEOMETRIES_STREAMED})
+
+
+def geometry(name: str) -> tuple:
+    """verifier_args.geometry -> (full table, its --small form)"""
+    both = {**GEOMETRIES, **GEOMETRIES_STREAMED}
+    if name not in both:
+        raise RFError(f"verifier_args.geometry {name!r} (one of {geometry_names()})")
+    return both[name]
 
 
 def tower_config(cfg: dict) -> dict:
@@ -56,8 +75,10 @@ class ClipScoreVerifier:
     runner.run_reflection_search.  `clip_state_dict`: an HF CLIPModel state dict (`text_model.*`, `vision_model.*`,
     `text_projection.weight`, `visual_projection.weight`, `logit_scale`); `tokenize(prompts) -> ids [B, L]` (CLIP BPE ids, EOS the
     largest id for the legacy eos_token_id = 2 config); height / width: the candidates' image size.  `model_config`: the head counts
-    and activation of the checkpoint's config.json (`text_heads`, `vision_heads`, `hidden_act`; what `load_clip_dir` returns);
-    None = clip-vit-large-patch14's (head dim 64 on both towers, quick_gelu)."""
+    and activation of the checkpoint's config.json (`text_heads`, `vision_heads`, `hidden_act`, `image_size`; what `load_clip_dir`
+    returns); None = clip-vit-large-patch14's (head dim 64 on both towers, quick_gelu).  The images are preprocessed at the
+    checkpoint's `image_size` (224, or 336 for clip-vit-large-patch14-336), cross-checked against its position-embedding rows; a
+    config without it takes the size those rows imply."""
 
     def __init__(self, pipe, clip_state_dict: Dict[str, torch.Tensor], tokenize: Callable[[List[str]], torch.Tensor], height: int, width: int,
                  eos_token_id: int = 2, eps: float = 1e-5, model_config: Optional[dict] = None):
@@ -80,7 +101,7 @@ class ClipScoreVerifier:
         if t_heads <= 0 or v_heads <= 0 or t_hidden % t_heads or v_hidden % v_heads:
             raise RFError(f"ClipScoreVerifier: {t_heads} / {v_heads} heads do not divide the hidden widths {t_hidden} / {v_hidden}")
         self.text = HipClipTextEncoder(text, t_heads, dev, eos_token_id=eos_token_id, eps=eps, head_dim=t_hidden // t_heads, act=act)
-        self.vision = HipClipVisionEncoder(vision, v_heads, dev, eps=eps, head_dim=v_hidden // v_heads, act=act)
+        self.vision = HipClipVisionEncoder(vision, v_heads, dev, eps=eps, head_dim=v_hidden // v_heads, act=act, image_size=mc.get("image_size"))
         self.text_projection = sd["text_projection.weight"].detach().to(dev, torch.bfloat16).contiguous()
         self.logit_scale = float(sd["logit_scale"].float())
         self._text_cache: Dict[str, torch.Tensor] = {}
@@ -226,7 +247,8 @@ def synthetic_tokenize(vocab: int, length: int = 77) -> Callable[[List[str]], to
 
 
 def read_clip_config(path: str) -> dict:
-    """What the verifier needs of an HF CLIPModel directory's config.json: head counts, activation, layer_norm_eps, projection_dim and
+    """What the verifier needs of an HF CLIPModel directory's config.json: head counts, activation, layer_norm_eps, projection_dim,
+    the vision tower's image_size (224 where the config leaves it out; 336 for clip-vit-large-patch14-336) and
     the text tower's eos_token_id (49407 in the LAION / PickScore configs: pooling at the first EOS; 2 in OpenAI's legacy configs:
     pooling at the largest id).  Keys a config leaves out take CLIPConfig's defaults."""
     with open(os.path.join(path, "config.json")) as f:
@@ -239,7 +261,8 @@ def read_clip_config(path: str) -> dict:
     if t_eps != v_eps:
         raise RFError(f"{path}: text layer_norm_eps {t_eps} != vision layer_norm_eps {v_eps}")
     return dict(text_heads=int(t.get("num_attention_heads", 8)), vision_heads=int(v.get("num_attention_heads", 12)), hidden_act=t_act,
-                layer_norm_eps=t_eps, projection_dim=int(cfg.get("projection_dim", 512)), eos_token_id=int(t.get("eos_token_id", 2)))
+                layer_norm_eps=t_eps, projection_dim=int(cfg.get("projection_dim", 512)), eos_token_id=int(t.get("eos_token_id", 2)),
+                image_size=int(v.get("image_size", 224)))
 
 
 def load_clip_dir(path: str):
@@ -264,18 +287,16 @@ def build_from_config(config: dict, pipe, synthetic: bool = False, small: bool =
     (clip-vit-large-patch14, or a ViT-H/14 one: PickScore_v1, HPSv2, LAION CLIP-H); its config.json decides heads and activation.
     "pickscore" is an alias: PickScore's score IS exp(logit_scale) * cos(image, text) behind the CLIP processor, a scalar metric
     sorted with `scalar_sort_key`.  With `synthetic`: a seeded random-init CLIP of `verifier_args.geometry` ("vit_l14", the default,
-    or "vit_h14"; their 2-layer TINY / TINY_H forms with `small`) and the synthetic tokenizer.  Switches the pipeline's VAE to the HIP path."""
+    "vit_h14" or "vit_l14_336"; their 2-layer TINY / TINY_H / TINY_336 forms with `small`) and the synthetic tokenizer.  Switches the pipeline's VAE to the HIP path."""
     va, pa = config.get("verifier_args", {}), config["pipeline_args"]
     if pipe.vae is None:
         raise RFError("the CLIP verifier needs a pipeline with a VAE")
     pipe.enable_hip_vae()
     if synthetic:
-        geo = va.get("geometry", "vit_l14")
-        if geo not in GEOMETRIES:
-            raise RFError(f"verifier_args.geometry {geo!r} (one of {sorted(GEOMETRIES)})")
-        cfg = GEOMETRIES[geo][1 if small else 0]
+        cfg = geometry(va.get("geometry", "vit_l14"))[1 if small else 0]
         seed = int(va.get("seed", 0))
-        sd, tok, mc = synthetic_clip_state(cfg, seed), synthetic_tokenize(cfg["text"]["vocab"]), dict(tower_config(cfg), eos_token_id=2)
+        sd, tok = synthetic_clip_state(cfg, seed), synthetic_tokenize(cfg["text"]["vocab"])
+        mc = dict(tower_config(cfg), eos_token_id=2, image_size=cfg["vision"]["image_size"])
     else:
         if not va.get("clip_model_path"):
             raise RFError(f'verifier_args.name == "{va.get("name", "clip")}" needs verifier_args.clip_model_path (an HF CLIPModel directory)')

@@ -1,10 +1,10 @@
 """Times the CLIP-score verifier's stages at 1024^2 (device events, one warm-up pass): FLUX VAE decode (synthetic FLUX-shaped HIP
 VAE), preprocess (rf_clip_preprocess, in place on the decoder's output), vision tower (rf_clip_vision_encode, synthetic weights of
---geometry: ViT-L/14, or ViT-H/14 = head dim 80 + erf GELU), score (rf_clip_score) and the text tower of one prompt, for n = 1, 8, 32
+--geometry: ViT-L/14, ViT-H/14 = head dim 80 + erf GELU, or ViT-L/14 at 336 px = 577 tokens on the streaming-keys attention), score (rf_clip_score) and the text tower of one prompt, for n = 1, 8, 32
 candidates.  --reps timed passes after the warm-up: the figures are medians, `vision_ms_spread` is max - min.  One further pass
 under ops.profile gives the towers' split by kernel class (`tower_us`: GEMM / attention / row kernels).  One JSON line per n.
 
-    python tools/kb_clip_score.py [--n 1 8 32] [--size 1024] [--geometry vit_l14|vit_h14] [--reps 1]
+    python tools/kb_clip_score.py [--n 1 8 32] [--size 1024] [--geometry vit_l14|vit_h14|vit_l14_336] [--reps 1]
 """
 import argparse
 import json
@@ -22,7 +22,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1, 8, 32])
     ap.add_argument("--size", type=int, default=1024)
-    ap.add_argument("--geometry", choices=["vit_l14", "vit_h14"], default="vit_l14")
+    ap.add_argument("--geometry", choices=["vit_l14", "vit_h14", "vit_l14_336"], default="vit_l14")
     ap.add_argument("--reps", type=int, default=1)
     args = ap.parse_args()
     from reflectionflow_amd import ops
@@ -33,11 +33,11 @@ def main():
     dev = torch.device("cuda:0")
     bf = torch.bfloat16
     vae = HipVAE(V.init_synthetic_vae_(V.AutoencoderKL(), seed=1).to(dev, bf).eval())
-    cfg = CV.GEOMETRIES[args.geometry][0]
+    cfg = CV.geometry(args.geometry)[0]
     t, v, act = cfg["text"], cfg["vision"], cfg.get("act", "quick_gelu")
     sd = CV.synthetic_clip_state(cfg, 0)
     enc = HipClipVisionEncoder({k: x for k, x in sd.items() if k.startswith("vision_model.") or k == "visual_projection.weight"}, v["heads"], dev,
-                               head_dim=v["hidden"] // v["heads"], act=act)
+                               head_dim=v["hidden"] // v["heads"], act=act, image_size=v["image_size"])
     tenc = HipClipTextEncoder({k: x for k, x in sd.items() if k.startswith("text_model.")}, t["heads"], dev, head_dim=t["hidden"] // t["heads"], act=act)
     ids = CV.synthetic_tokenize(t["vocab"])(["a red cube left of a blue ball"]).to(dev)
     txt = torch.randn(cfg["projection_dim"], device=dev).to(bf)
