@@ -444,7 +444,12 @@ typedef struct rf_vae_weights {                 /* ONE direction: the Decoder or
                                                    encoder = downsampler conv (3x3, stride 2, pad (0,1,0,1)); w NULL = none */
   rf_vae_norm norm_out; rf_vae_conv conv_out;
 } rf_vae_weights;
-/* workspace (caller-owned, 256-byte aligned) for an input of h x w pixels (decode: latent size, encode: image size) */
+/* workspace (caller-owned, 256-byte aligned) for an input of h x w pixels (decode: latent size, encode: image size).
+ * Its CONTENTS on entry do not matter (a fresh hipMalloc, another call's leftovers, NaN): every word a launch reads was written by
+ * an earlier launch of the same call.  That includes the up to fold - 1 pixels behind an image that the last GEMM row of a folded
+ * convolution multiplies against zero weight columns (0 x NaN is NaN): the kernels that produce a convolution's input write zeros
+ * over the 64 pixels behind it, and the size returned here has the room.  The one buffer the library cannot prepare is the
+ * caller's input -- INPUT SLACK below. */
 int64_t rf_vae_workspace_bytes(const rf_vae_weights* w, int32_t encode, int32_t h, int32_t w_in);
 /* INPUT SLACK (both entry points): conv_in runs as a GEMM whose 64-element K-tiles reach past the last pixel's channels against zero
  * weight columns, so the input buffer must be followed by >= 64 * max(conv_in.cin, 64) * 2 readable bytes holding FINITE values

@@ -8,6 +8,7 @@
  *   rf_debug_sk_plan, rf_debug_attn_mix_plan   the host-side work plans (pure arithmetic, callable without a GPU)
  *   rf_debug_clock_probe     the shader clock a probed launch saw (rf_gemm_desc.clock_probe / an open profile)
  *   rf_debug_text_attention  one launch of the text / CLIP towers' attention kernels on caller buffers (kernel-level parity tests)
+ *   rf_debug_vae_op          one op of the VAE (GroupNorm, 3x3 convolution, upsample, downsample, attention) on caller buffers
  */
 #ifndef RF_FLUX_DEBUG_H
 #define RF_FLUX_DEBUG_H
@@ -74,6 +75,40 @@ int rf_debug_clock_probe(int which, double* mhz, double* us);
 int rf_debug_text_attention(int32_t head_dim, int32_t qi, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
                             const float* bias, int64_t bias_hs, void* out, int64_t ldo, int32_t heads, int32_t B, int32_t S, int32_t S_pad,
                             float scale, void* stream);
+
+/* ONE op of the VAE (csrc/vae.hip) on caller buffers, through the host functions rf_vae_decode / rf_vae_encode run (same grids, same
+ * kernel instantiations, same fold / schedule decisions).  Images are zero-halo NHWC bf16 as in rf_flux.h; "compact" = [H*W][C] without
+ * the halo.  Every argument is validated before the first HIP call.  Not a switch: it changes nothing about any other launch.
+ *   GROUP_NORM  out = [silu](group_norm(in)); in padded [(H+2)(W+2)][C] (its halo is not read), `norm`, `groups`; out compact, or padded
+ *               with a zero halo FOLLOWED BY RF_VAE_TAIL_PIXELS zeroed pixels (what a folded convolution behind it may read)
+ *   CONV3X3     out = [residual +] conv(in); in padded [..][conv->cin] with a CLEAN zero halo (+ the tail above when it runs folded), out /
+ *               residual padded [..][conv->cout]; residual may alias out.  Rows (W+3) .. of out are written: the interior, the halo columns
+ *               between (garbage) and, folded, up to fold - 1 pixels of the bottom halo row
+ *   UPSAMPLE2X  in padded [(H+2)(W+2)][C] (halo not read) -> out padded [(2H+2)(2W+2)][C], zero halo + zeroed tail as GROUP_NORM
+ *   DOWNSAMPLE  3x3 / stride 2 over F.pad(in, (0,1,0,1)): in padded [(H+2)(W+2)][conv->cin] (halo not read), H, W even -> out padded
+ *               [(H/2+2)(W/2+2)][conv->cout], rows (W/2+3) .. written as CONV3X3 (conv->w in the plain [cout][3][3][cin] layout)
+ *   ATTN_CORE   vae_attn_kernel alone: in = qk [S][1024] (q | k), residual = vt [512][S], out [S][512]; S = H*W, C = 512
+ *   ATTN_BLOCK  the mid-block attention in place: out = padded [(H+2)(W+2)][512], x += to_out(attn(group_norm(x))); halo neither read
+ *               nor written; `attn`, `groups`; `in` unused
+ * ws == NULL (or ws->base == NULL): returns the workspace bytes the op needs (> 0) instead of running; the workspace's contents on
+ * entry do not matter.  Otherwise returns RF_OK or an RF_ERR_* status. */
+#define RF_VAE_TAIL_PIXELS 64
+typedef enum rf_vae_op {
+  RF_VAE_OP_GROUP_NORM = 0, RF_VAE_OP_CONV3X3 = 1, RF_VAE_OP_UPSAMPLE2X = 2, RF_VAE_OP_DOWNSAMPLE = 3, RF_VAE_OP_ATTN_CORE = 4,
+  RF_VAE_OP_ATTN_BLOCK = 5
+} rf_vae_op;
+typedef struct rf_vae_op_desc {
+  int32_t op;                       /* rf_vae_op */
+  int32_t H, W, C, groups;          /* INPUT geometry; C: GROUP_NORM / UPSAMPLE2X / ATTN_* (the convolutions carry cin / cout) */
+  int32_t silu, compact;            /* GROUP_NORM */
+  int32_t _pad;
+  const rf_vae_norm* norm;          /* GROUP_NORM */
+  const rf_vae_conv* conv;          /* CONV3X3, DOWNSAMPLE */
+  const rf_vae_attn* attn;          /* ATTN_BLOCK */
+  const void* in; void* out; const void* residual;
+  const rf_workspace* ws;
+} rf_vae_op_desc;
+int64_t rf_debug_vae_op(const rf_vae_op_desc* d, void* stream);
 
 #ifdef __cplusplus
 }

@@ -142,6 +142,17 @@ class rf_vae_weights(C.Structure):
                 ("norm_out", rf_vae_norm), ("conv_out", rf_vae_conv)]
 
 
+class rf_vae_op_desc(C.Structure):
+    """include/rf_flux_debug.h: one VAE op on caller buffers (rf_debug_vae_op)"""
+    _fields_ = [(n, C.c_int32) for n in ("op", "H", "W", "C", "groups", "silu", "compact", "_pad")] + [
+        ("norm", C.POINTER(rf_vae_norm)), ("conv", C.POINTER(rf_vae_conv)), ("attn", C.POINTER(rf_vae_attn)),
+        ("input", _P), ("out", _P), ("residual", _P), ("ws", C.POINTER(rf_workspace))]
+
+
+RF_VAE_OP_GROUP_NORM, RF_VAE_OP_CONV3X3, RF_VAE_OP_UPSAMPLE2X, RF_VAE_OP_DOWNSAMPLE, RF_VAE_OP_ATTN_CORE, RF_VAE_OP_ATTN_BLOCK = range(6)
+RF_VAE_TAIL_PIXELS = 64
+
+
 class rf_t5_layer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ln0", "w_qk", "w_v", "w_o", "ln1", "w_wi", "w_wo")]
 
@@ -280,7 +291,9 @@ _EXTRA_SIGS = {
                "rf_debug_attn_mix_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
                # (head_dim, qi, q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, heads, B, S, S_pad, scale, stream)
                "rf_debug_text_attention": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64,
-                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P])}
+                                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
+               # one VAE op on caller buffers; workspace bytes when desc.ws is NULL, else a status
+               "rf_debug_vae_op": (C.c_int64, [C.POINTER(rf_vae_op_desc), _P])}
 _lib = None
 
 

@@ -131,13 +131,14 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
   }
 }
 
-// pass 3: y = act(x * a + b) on interior pixels; padded output gets a clean zero halo, compact output drops the halo
+// pass 3: y = act(x * a + b) on interior pixels; padded output gets a clean zero halo and `tail` zeroed pixels behind the image (what
+// a folded convolution's last GEMM row reads past it, see conv3x3), compact output drops the halo
 template <bool SILU, bool COMPACT>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int H, int W, int C,
-                                                       const float* __restrict__ ab) {
+                                                       const float* __restrict__ ab, int tail) {
   const int tpp = C / 8;
   const int Wp = W + 2;
-  const int64_t total = (int64_t)(H + 2) * Wp * tpp;
+  const int64_t total = ((int64_t)(H + 2) * Wp + (COMPACT ? 0 : tail)) * tpp;
   const int64_t stride = (int64_t)gridDim.x * 256;          // a multiple of tpp (tpp divides 256)
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int cs = (int)(i % tpp);
@@ -172,11 +173,12 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const bf16_t* __restrict_
   }
 }
 
-// nearest 2x upsample, padded [h+2][w+2][C] -> padded [2h+2][2w+2][C] with a zero halo  (Upsample2D: interpolate(scale 2, nearest))
-__global__ __launch_bounds__(256) void upsample2x_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int h, int w, int C) {
+// nearest 2x upsample, padded [h+2][w+2][C] -> padded [2h+2][2w+2][C] with a zero halo and `tail` zeroed pixels behind the image (as
+// gn_apply_kernel)  (Upsample2D: interpolate(scale 2, nearest))
+__global__ __launch_bounds__(256) void upsample2x_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int h, int w, int C, int tail) {
   const int tpp = C / 8;
   const int Wo = 2 * w + 2, Wi = w + 2;
-  const int64_t total = (int64_t)(2 * h + 2) * Wo * tpp;
+  const int64_t total = ((int64_t)(2 * h + 2) * Wo + tail) * tpp;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int cs = (int)(i % tpp);
     const int64_t p = i / tpp;
@@ -439,6 +441,10 @@ struct VaeCtx {
   void* sk; int64_t sk_bytes;  // GEMM scratch (stream-K flags + partial tiles)
 };
 constexpr int GN_BLOCKS = 2048;
+// pixels behind every padded image a convolution reads: a folded convolution's last GEMM row multiplies up to fold - 1 pixels past the
+// image against the zero columns of wf, and 0 x NaN is NaN inside an MFMA -- so the producers (gn_apply_kernel, upsample2x_kernel)
+// write zeros there and the result never depends on what the workspace held on entry.  vae_sizes() reserves the room.
+constexpr int VAE_TAIL = RF_VAE_TAIL_PIXELS;
 
 static inline int64_t padded_elems(int H, int W, int C) { return (int64_t)(H + 2) * (W + 2) * C; }
 
@@ -448,12 +454,38 @@ static inline int64_t padded_elems(int H, int W, int C) { return (int64_t)(H + 2
     if (_rc != RF_OK) return _rc; \
   } while (0)
 
-static int group_norm(VaeCtx& c, const rf_vae_norm& n, const bf16_t* x, bf16_t* y, int H, int W, int C, bool silu, bool compact) {
+// the refusals of each op, apart from its launches: rf_debug_vae_op runs them before its first HIP call
+static int group_norm_check(const rf_vae_norm& n, int C, int groups) {
   RF_REQUIRE(n.gamma && n.beta, RF_ERR_NULL, "rf_vae: GroupNorm weights NULL");
-  const int cpg = c.w->groups > 0 ? C / c.w->groups : 0;
-  RF_REQUIRE(C % 8 == 0 && 256 % (C / 8) == 0 && C <= 512 && c.w->groups > 0 && C % c.w->groups == 0 &&
+  const int cpg = groups > 0 ? C / groups : 0;
+  RF_REQUIRE(C >= 8 && C % 8 == 0 && 256 % (C / 8) == 0 && C <= 512 && groups > 0 && C % groups == 0 &&
                  (cpg == 2 || cpg == 4 || cpg == 8 || cpg == 16), RF_ERR_SHAPE,
-             "rf_vae: GroupNorm over C=%d channels, %d groups is not supported (C in {64,128,256,512}, 2..16 channels per group)", C, c.w->groups);
+             "rf_vae: GroupNorm over C=%d channels, %d groups is not supported (C in {64,128,256,512}, 2..16 channels per group)", C, groups);
+  return RF_OK;
+}
+
+static int conv3x3_check(const rf_vae_conv& cv) {
+  RF_REQUIRE(cv.w && cv.cin > 0 && cv.cout > 0 && cv.cin % 64 == 0 && cv.cout % 8 == 0 && cv.cout <= 1024, RF_ERR_SHAPE,
+             "rf_vae: conv3x3 %d -> %d (need cin %% 64 == 0, cout %% 8 == 0)", cv.cin, cv.cout);
+  RF_REQUIRE(cv.wf == nullptr || cv.fold <= VAE_TAIL + 1, RF_ERR_SHAPE, "rf_vae: conv3x3 fold=%d (at most %d: the zeroed tail behind an image)", cv.fold,
+             VAE_TAIL + 1);
+  return RF_OK;
+}
+
+static int downsample_check(const rf_vae_conv& cv, int H, int W) {
+  RF_REQUIRE(cv.w && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && cv.cin > 0 && cv.cout > 0 && cv.cin % 64 == 0 && cv.cout % 8 == 0, RF_ERR_SHAPE,
+             "rf_vae_encode: downsample of %dx%dx%d", H, W, cv.cin);
+  return RF_OK;
+}
+
+static int attention_check(int C, int S) {
+  RF_REQUIRE(C == VA_C, RF_ERR_UNSUPPORTED, "rf_vae: the attention kernel is built for %d channels (got %d)", VA_C, C);
+  RF_REQUIRE(S > 0 && S % 64 == 0, RF_ERR_SHAPE, "rf_vae: attention over %d tokens (need a multiple of 64)", S);
+  return RF_OK;
+}
+
+static int group_norm(VaeCtx& c, const rf_vae_norm& n, const bf16_t* x, bf16_t* y, int H, int W, int C, bool silu, bool compact) {
+  RF_TRY(group_norm_check(n, C, c.w->groups));
   const int64_t npix = (int64_t)(H + 2) * (W + 2);
   const int nblk = (int)(npix < GN_BLOCKS * 64 ? cdiv64(npix, 64) : GN_BLOCKS);
   const int ppb = (int)cdiv64(npix, nblk);
@@ -469,11 +501,11 @@ static int group_norm(VaeCtx& c, const rf_vae_norm& n, const bf16_t* x, bf16_t* 
                      (double)H * W * (C / c.w->groups), 1e-6f, (const bf16_t*)n.gamma, (const bf16_t*)n.beta, c.ab);
   const int grid = grid_for(npix * (C / 8));
   if (compact) {
-    if (silu) hipLaunchKernelGGL((gn_apply_kernel<true, true>), dim3(grid), dim3(256), 0, c.st, x, y, H, W, C, c.ab);
-    else hipLaunchKernelGGL((gn_apply_kernel<false, true>), dim3(grid), dim3(256), 0, c.st, x, y, H, W, C, c.ab);
+    if (silu) hipLaunchKernelGGL((gn_apply_kernel<true, true>), dim3(grid), dim3(256), 0, c.st, x, y, H, W, C, c.ab, VAE_TAIL);
+    else hipLaunchKernelGGL((gn_apply_kernel<false, true>), dim3(grid), dim3(256), 0, c.st, x, y, H, W, C, c.ab, VAE_TAIL);
   } else {
-    if (silu) hipLaunchKernelGGL((gn_apply_kernel<true, false>), dim3(grid), dim3(256), 0, c.st, x, y, H, W, C, c.ab);
-    else hipLaunchKernelGGL((gn_apply_kernel<false, false>), dim3(grid), dim3(256), 0, c.st, x, y, H, W, C, c.ab);
+    if (silu) hipLaunchKernelGGL((gn_apply_kernel<true, false>), dim3(grid), dim3(256), 0, c.st, x, y, H, W, C, c.ab, VAE_TAIL);
+    else hipLaunchKernelGGL((gn_apply_kernel<false, false>), dim3(grid), dim3(256), 0, c.st, x, y, H, W, C, c.ab, VAE_TAIL);
   }
   RF_LAUNCH_CHECK();
   return RF_OK;
@@ -487,10 +519,11 @@ static void set_seg(rf_kseg& s, const void* A, int64_t lda, const void* W, int64
 // Narrow outputs run FOLDED when the packer provided the copy (rf_vae_conv.wf) and the image is wide enough: g adjacent output
 // pixels are one GEMM row -- A rows of (g+2) Cin taps at a pitch of g Cin, N = g Cout -- so a cout = 128 layer fills the 256-column
 // MFMA tile (1.5x fewer MFMAs than half-empty tiles) and the 8-channel conv_out 2.8x fewer.  The last row may run up to g-1
-// pixels past the last interior pixel: those land in the bottom halo row (g <= W + 3), whose content nobody reads.
+// pixels past the last interior pixel: those land in the bottom halo row (g <= W + 3), whose content nobody reads.  That row READS up
+// to g-1 pixels past the end of x, against zero weight columns: they must be finite -- the zeroed tail its producer wrote (VAE_TAIL), or
+// the caller's zeroed slack behind the input of conv_in (rf_flux.h, INPUT SLACK).
 static int conv3x3(VaeCtx& c, const rf_vae_conv& cv, const bf16_t* x, bf16_t* y, int H, int W, const bf16_t* residual) {
-  RF_REQUIRE(cv.w && cv.cin % 64 == 0 && cv.cout % 8 == 0 && cv.cout <= 1024, RF_ERR_SHAPE, "rf_vae: conv3x3 %d -> %d (need cin %% 64 == 0, cout %% 8 == 0)",
-             cv.cin, cv.cout);
+  RF_TRY(conv3x3_check(cv));
   RF_REQUIRE(padded_elems(H, W, cv.cin > cv.cout ? cv.cin : cv.cout) * 2 <= c.cap, RF_ERR_WORKSPACE, "rf_vae: activation %dx%dx%d exceeds the workspace buffers",
              H, W, cv.cin > cv.cout ? cv.cin : cv.cout);
   const int Wp = W + 2, Ci = cv.cin, Co = cv.cout;
@@ -562,31 +595,61 @@ static int resnet(VaeCtx& c, const rf_vae_resnet& r, int H, int W) {
   return conv3x3(c, r.conv2, c.T1, c.X, H, W, res);   // out may alias the residual (Ci == Co) -- the epilogue reads before it writes
 }
 
+// out [S][C] = softmax(q k^T / sqrt(C)) v  for qk [S][2C] (q | k), vt [C][S]: the one launch site of vae_attn_kernel
+static int attention_core(hipStream_t st, const bf16_t* qk, const bf16_t* vt, bf16_t* out, int S, int C) {
+  RF_TRY(attention_check(C, S));
+  static bool attr_set = false;
+  if (!attr_set) {
+    RF_CHECK_HIP(hipFuncSetAttribute((const void*)vae_attn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, VA_LDS));
+    attr_set = true;
+  }
+  ProfScope prof(RF_KC_ATTN, 4.0 * (double)S * S * C, st);
+  hipLaunchKernelGGL(vae_attn_kernel, dim3(S / 64), dim3(512), VA_LDS, st, qk, vt, out, S, 1.4426950408889634f / sqrtf((float)C));
+  RF_LAUNCH_CHECK();
+  return RF_OK;
+}
+
+static int attention_weights_check(const rf_vae_attn& a) {
+  RF_REQUIRE(a.w_qk && a.w_v && a.w_out, RF_ERR_NULL, "rf_vae: attention weights NULL");
+  return RF_OK;
+}
+
 // mid-block attention, in place on c.X: x += to_out(softmax(q k^T / sqrt(C)) v),  q, k, v = linear(group_norm(x))
 static int attention(VaeCtx& c, const rf_vae_attn& a, int H, int W) {
   const int C = a.C, S = H * W;
-  RF_REQUIRE(C == VA_C, RF_ERR_UNSUPPORTED, "rf_vae: the attention kernel is built for %d channels (got %d)", VA_C, C);
-  RF_REQUIRE(S % 64 == 0, RF_ERR_SHAPE, "rf_vae: attention over %d tokens (need a multiple of 64)", S);
-  RF_REQUIRE(a.w_qk && a.w_v && a.w_out, RF_ERR_NULL, "rf_vae: attention weights NULL");
+  RF_TRY(attention_check(C, S));
+  RF_TRY(attention_weights_check(a));
   bf16_t* xn = c.T1;                                               // compact [S][C]
   RF_TRY(group_norm(c, a.norm, c.X, xn, H, W, C, false, true));
   RF_TRY(linear(c, xn, C, a.w_qk, a.b_qk, S, 2 * C, C, c.aqk, 2 * C));
   RF_TRY(linear(c, (const bf16_t*)a.w_v, C, xn, nullptr, C, S, C, c.avt, S));   // V^T = W_v . xn^T  (operands swapped)
-  {
-    static bool attr_set = false;
-    if (!attr_set) {
-      RF_CHECK_HIP(hipFuncSetAttribute((const void*)vae_attn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, VA_LDS));
-      attr_set = true;
-    }
-    ProfScope prof(RF_KC_ATTN, 4.0 * (double)S * S * C, c.st);
-    hipLaunchKernelGGL(vae_attn_kernel, dim3(S / 64), dim3(512), VA_LDS, c.st, c.aqk, c.avt, c.ao, S,
-                       1.4426950408889634f / sqrtf((float)C));
-    RF_LAUNCH_CHECK();
-  }
+  RF_TRY(attention_core(c.st, c.aqk, c.avt, c.ao, S, C));
   RF_TRY(linear(c, c.ao, C, a.w_out, a.b_out, S, C, C, c.T2, C));
   hipLaunchKernelGGL(add_compact_kernel, dim3(grid_for((int64_t)S * (C / 8))), dim3(256), 0, c.st, c.X, c.T2, H, W, C);
   RF_LAUNCH_CHECK();
   return RF_OK;
+}
+
+// Upsample2D's interpolation: padded [H+2][W+2][C] -> padded [2H+2][2W+2][C]  (its convolution follows as a conv3x3)
+static int upsample2x(VaeCtx& c, const bf16_t* x, bf16_t* y, int H, int W, int C) {
+  ProfScope prof(RF_KC_ROWOP, 5.0 * (double)H * W * C * 2, c.st);
+  hipLaunchKernelGGL(upsample2x_kernel, dim3(grid_for(padded_elems(2 * H, 2 * W, C) / 8)), dim3(256), 0, c.st, x, y, H, W, C, VAE_TAIL);
+  RF_LAUNCH_CHECK();
+  return RF_OK;
+}
+
+// Downsample2D(padding = 0): 3x3 / stride 2 over F.pad(x, (0, 1, 0, 1)) as im2col (c.col) + one GEMM; y: padded [H/2+2][W/2+2][cout],
+// written from row W/2 + 3 on (interior + the halo columns between)
+static int downsample(VaeCtx& c, const rf_vae_conv& cv, const bf16_t* x, bf16_t* y, int H, int W) {
+  RF_TRY(downsample_check(cv, H, W));
+  const int Ho = H / 2, Wo = W / 2, Ci = cv.cin, Co = cv.cout;
+  const int64_t M = (int64_t)(Ho - 1) * (Wo + 2) + Wo;
+  {
+    ProfScope prof(RF_KC_ROWOP, 2.0 * (double)M * 9 * Ci * 2, c.st);
+    hipLaunchKernelGGL(im2col_s2_kernel, dim3(grid_for(M * (9 * Ci / 8))), dim3(256), 0, c.st, x, c.col, H, W, Ci);
+    RF_LAUNCH_CHECK();
+  }
+  return linear(c, c.col, 9 * Ci, cv.w, cv.b, (int)M, Co, 9 * Ci, y + (int64_t)(Wo + 3) * Co, Co);
 }
 
 struct VaeSizes { int64_t cap, attn_qk, attn_vt, attn_o, col, total; };
@@ -630,7 +693,7 @@ static VaeSizes vae_sizes(const rf_vae_weights* w, int encode, int h, int wd) {
   const int Hm = encode ? H : h, Wm = encode ? W : wd;
   const int Cm = w->mid0.conv1.cin;
   see(Hm, Wm, Cm);
-  z.cap = round_up(cap + 64 * 512 * 2, 256);   // + 64 pixels of slack: a folded convolution's last row reads up to fold - 1 pixels past the image
+  z.cap = round_up(cap + VAE_TAIL * 512 * 2, 256);   // + the zeroed tail behind an image (a folded convolution's last row reads up to fold - 1 pixels of it)
   if (w->has_attn) {
     const int64_t S = (int64_t)Hm * Wm;
     z.attn_qk = round_up(S * 2 * Cm * 2, 256);
@@ -642,6 +705,14 @@ static VaeSizes vae_sizes(const rf_vae_weights* w, int encode, int h, int wd) {
   z.total = 4 * z.cap + z.attn_qk + z.attn_vt + z.attn_o + z.col + round_up(1024 * 2, 256) + round_up((int64_t)GN_BLOCKS * 512 * 2 * 4, 256) +
             round_up(2 * 512 * 4, 256) + sk;
   return z;
+}
+
+// what a call needs from its workspace before the first op: the gate of ones, clean stream-K flags (everything else is written before it is read)
+static int vae_ctx_prime(VaeCtx& c) {
+  hipLaunchKernelGGL(fill_bf16_kernel, dim3(4), dim3(256), 0, c.st, c.ones, (int64_t)1024, 1.0f);
+  RF_CHECK_HIP(hipMemsetAsync(c.sk, 0, 4096, c.st));          // stream-K flags: zero before the first launch
+  RF_LAUNCH_CHECK();
+  return RF_OK;
 }
 
 static int vae_ctx(VaeCtx& c, const rf_vae_weights* w, int encode, int h, int wd, const rf_workspace* ws, hipStream_t st) {
@@ -662,10 +733,7 @@ static int vae_ctx(VaeCtx& c, const rf_vae_weights* w, int encode, int h, int wd
   c.part = (float*)take((int64_t)GN_BLOCKS * 512 * 2 * 4);
   c.ab = (float*)take(2 * 512 * 4);
   c.sk = take(4096 + (64ll << 20)); c.sk_bytes = 4096 + (64ll << 20);
-  hipLaunchKernelGGL(fill_bf16_kernel, dim3(4), dim3(256), 0, st, c.ones, (int64_t)1024, 1.0f);
-  RF_CHECK_HIP(hipMemsetAsync(c.sk, 0, 4096, st));          // stream-K flags: zero before the first launch
-  RF_LAUNCH_CHECK();
-  return RF_OK;
+  return vae_ctx_prime(c);
 }
 
 }  // namespace rf
@@ -694,11 +762,7 @@ extern "C" int rf_vae_decode(const rf_vae_weights* w, const void* z, int32_t h, 
     if (w->resample[i].w) {
       const int C = w->resample[i].cin;
       RF_REQUIRE(padded_elems(2 * H, 2 * W, C) * 2 <= c.cap, RF_ERR_WORKSPACE, "rf_vae_decode: upsampled activation exceeds the workspace");
-      {
-        ProfScope prof(RF_KC_ROWOP, 5.0 * (double)H * W * C * 2, st);
-        hipLaunchKernelGGL(upsample2x_kernel, dim3(grid_for(padded_elems(2 * H, 2 * W, C) / 8)), dim3(256), 0, st, c.X, c.T1, H, W, C);
-        RF_LAUNCH_CHECK();
-      }
+      RF_TRY(upsample2x(c, c.X, c.T1, H, W, C));
       H *= 2; W *= 2;
       RF_TRY(conv3x3(c, w->resample[i], c.T1, c.X, H, W, nullptr));
     }
@@ -720,19 +784,10 @@ extern "C" int rf_vae_encode(const rf_vae_weights* w, const void* img, int32_t H
   for (int i = 0; i < w->levels; ++i) {
     for (int j = 0; j < w->res_per_level; ++j) RF_TRY(resnet(c, w->res[i][j], H, W));
     if (w->resample[i].w) {
-      const rf_vae_conv& cv = w->resample[i];
-      RF_REQUIRE(H % 2 == 0 && W % 2 == 0 && cv.cin % 64 == 0 && cv.cout % 8 == 0, RF_ERR_SHAPE, "rf_vae_encode: downsample of %dx%dx%d", H, W, cv.cin);
-      const int Ho = H / 2, Wo = W / 2, Ci = cv.cin, Co = cv.cout;
-      const int64_t M = (int64_t)(Ho - 1) * (Wo + 2) + Wo;
-      {
-        ProfScope prof(RF_KC_ROWOP, 2.0 * (double)M * 9 * Ci * 2, st);
-        hipLaunchKernelGGL(im2col_s2_kernel, dim3(grid_for(M * (9 * Ci / 8))), dim3(256), 0, st, c.X, c.col, H, W, Ci);
-        RF_LAUNCH_CHECK();
-      }
-      RF_TRY(linear(c, c.col, 9 * Ci, cv.w, cv.b, (int)M, Co, 9 * Ci, c.T1 + (int64_t)(Wo + 3) * Co, Co));
+      RF_TRY(downsample(c, w->resample[i], c.X, c.T1, H, W));
       // (the result is a residual stream: nobody reads its halo -- GroupNorm / im2col skip it and write clean halos for what a conv reads)
       bf16_t* t = c.X; c.X = c.T1; c.T1 = t;
-      H = Ho; W = Wo;
+      H /= 2; W /= 2;
     }
   }
   RF_TRY(resnet(c, w->mid0, H, W));
@@ -740,4 +795,94 @@ extern "C" int rf_vae_encode(const rf_vae_weights* w, const void* img, int32_t H
   RF_TRY(resnet(c, w->mid1, H, W));
   RF_TRY(group_norm(c, w->norm_out, c.X, c.T1, H, W, w->conv_out.cin, true, false));
   return conv3x3(c, w->conv_out, c.T1, (bf16_t*)out, H, W, nullptr);
+}
+
+// ---- one op on caller buffers (include/rf_flux_debug.h): the kernel-level parity tests ----------------------------------------
+// Workspace of an op: what every op shares (ones, GroupNorm partials, affine, GEMM scratch), then the buffers the op itself needs.
+struct VaeOpSizes { int64_t col, t, aqk, avt, ao, total; };
+
+static VaeOpSizes vae_op_sizes(const rf_vae_op_desc* d) {
+  VaeOpSizes z;
+  memset(&z, 0, sizeof(z));
+  const int64_t S = (int64_t)d->H * d->W;
+  if (d->op == RF_VAE_OP_DOWNSAMPLE) z.col = round_up((int64_t)(d->H / 2) * (d->W / 2 + 2) * 9 * d->conv->cin * 2, 256);
+  if (d->op == RF_VAE_OP_ATTN_BLOCK) {
+    z.t = round_up(S * VA_C * 2, 256);          // T1 (compact normalised x) and T2 (compact out-projection)
+    z.aqk = round_up(S * 2 * VA_C * 2, 256);
+    z.avt = z.ao = round_up(S * VA_C * 2, 256);
+  }
+  z.total = round_up(1024 * 2, 256) + round_up((int64_t)GN_BLOCKS * 512 * 2 * 4, 256) + round_up(2 * 512 * 4, 256) + 4096 + (64ll << 20) + z.col + 2 * z.t +
+            z.aqk + z.avt + z.ao;
+  return z;
+}
+
+extern "C" int64_t rf_debug_vae_op(const rf_vae_op_desc* d, void* stream) {
+  const char* who = "rf_debug_vae_op";
+  RF_REQUIRE(d, RF_ERR_NULL, "%s: descriptor NULL", who);
+  RF_REQUIRE(d->op >= RF_VAE_OP_GROUP_NORM && d->op <= RF_VAE_OP_ATTN_BLOCK, RF_ERR_UNSUPPORTED, "%s: op=%d", who, d->op);
+  RF_REQUIRE(d->H > 0 && d->W > 0 && d->H <= 8192 && d->W <= 8192, RF_ERR_SHAPE, "%s: H=%d W=%d", who, d->H, d->W);
+  const int H = d->H, W = d->W, C = d->C;
+  switch (d->op) {
+    case RF_VAE_OP_GROUP_NORM:
+      RF_REQUIRE(d->norm, RF_ERR_NULL, "%s: GROUP_NORM without norm", who);
+      RF_TRY(group_norm_check(*d->norm, C, d->groups));
+      break;
+    case RF_VAE_OP_CONV3X3:
+      RF_REQUIRE(d->conv, RF_ERR_NULL, "%s: CONV3X3 without conv", who);
+      RF_TRY(conv3x3_check(*d->conv));
+      break;
+    case RF_VAE_OP_UPSAMPLE2X:
+      RF_REQUIRE(C >= 8 && C % 8 == 0 && C <= 512, RF_ERR_SHAPE, "%s: UPSAMPLE2X over C=%d channels (need a multiple of 8, at most 512)", who, C);
+      break;
+    case RF_VAE_OP_DOWNSAMPLE:
+      RF_REQUIRE(d->conv, RF_ERR_NULL, "%s: DOWNSAMPLE without conv", who);
+      RF_TRY(downsample_check(*d->conv, H, W));
+      break;
+    case RF_VAE_OP_ATTN_CORE:
+      RF_TRY(attention_check(C, H * W));
+      RF_REQUIRE(d->residual, RF_ERR_NULL, "%s: ATTN_CORE without vt (residual)", who);
+      break;
+    default:   // RF_VAE_OP_ATTN_BLOCK
+      RF_REQUIRE(d->attn, RF_ERR_NULL, "%s: ATTN_BLOCK without attn", who);
+      RF_REQUIRE(d->attn->C == C, RF_ERR_SHAPE, "%s: attn->C=%d but C=%d", who, d->attn->C, C);
+      RF_TRY(attention_check(C, H * W));
+      RF_TRY(attention_weights_check(*d->attn));
+      RF_TRY(group_norm_check(d->attn->norm, C, d->groups));
+      break;
+  }
+  const VaeOpSizes z = vae_op_sizes(d);
+  if (!d->ws || !d->ws->base) return z.total;
+  RF_REQUIRE(aligned16(d->ws->base) && d->ws->bytes >= z.total, RF_ERR_WORKSPACE, "%s: workspace %lld < required %lld bytes (or not 16-byte aligned)", who,
+             (long long)d->ws->bytes, (long long)z.total);
+  RF_REQUIRE(d->out && (d->in || d->op == RF_VAE_OP_ATTN_BLOCK), RF_ERR_NULL, "%s: NULL tensor", who);
+  RF_REQUIRE(aligned16(d->in) && aligned16(d->out) && aligned16(d->residual), RF_ERR_ALIGN, "%s: tensors must be 16-byte aligned", who);
+
+  rf_vae_weights wt;
+  memset(&wt, 0, sizeof(wt));
+  wt.groups = d->groups;
+  VaeCtx c;
+  memset(&c, 0, sizeof(c));
+  c.w = &wt; c.st = (hipStream_t)stream; c.base = (char*)d->ws->base;
+  c.cap = INT64_MAX;                            // the images are the caller's
+  char* p = c.base;
+  auto take = [&](int64_t bytes) { char* q = p; p += round_up(bytes, 256); return q; };
+  c.ones = (bf16_t*)take(1024 * 2);
+  c.part = (float*)take((int64_t)GN_BLOCKS * 512 * 2 * 4);
+  c.ab = (float*)take(2 * 512 * 4);
+  c.sk = take(4096 + (64ll << 20)); c.sk_bytes = 4096 + (64ll << 20);
+  c.col = (bf16_t*)take(z.col);
+  c.T1 = (bf16_t*)take(z.t); c.T2 = (bf16_t*)take(z.t);
+  c.aqk = (bf16_t*)take(z.aqk); c.avt = (bf16_t*)take(z.avt); c.ao = (bf16_t*)take(z.ao);
+  c.X = (bf16_t*)d->out;                        // ATTN_BLOCK runs in place
+  RF_TRY(vae_ctx_prime(c));
+  const bf16_t* in = (const bf16_t*)d->in;
+  bf16_t* out = (bf16_t*)d->out;
+  switch (d->op) {
+    case RF_VAE_OP_GROUP_NORM: return group_norm(c, *d->norm, in, out, H, W, C, d->silu != 0, d->compact != 0);
+    case RF_VAE_OP_CONV3X3: return conv3x3(c, *d->conv, in, out, H, W, (const bf16_t*)d->residual);
+    case RF_VAE_OP_UPSAMPLE2X: return upsample2x(c, in, out, H, W, C);
+    case RF_VAE_OP_DOWNSAMPLE: return downsample(c, *d->conv, in, out, H, W);
+    case RF_VAE_OP_ATTN_CORE: return attention_core(c.st, in, (const bf16_t*)d->residual, out, H * W, C);
+    default: return attention(c, *d->attn, H, W);
+  }
 }

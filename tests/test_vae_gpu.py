@@ -9,10 +9,9 @@ Tolerance (floating point, bf16 storage / fp32 accumulation vs an fp32 oracle): 
 judged relative to eager PyTorch bf16 on the same inputs -- rel-L2(hip, fp32) <= 2 x rel-L2(torch_bf16, fp32) + 2e-3 -- where
 torch bf16 = the flux/vae.py modules in bf16 on the CPU (small cases).  At the full 1024^2 decode (no affordable bf16 torch
 run: MIOpen's search costs minutes per shape) the bound is the calibrated constant stated in the test.
-Cases: every kernel class on its own (conv as 3-segment GEMM incl. channel padding and ragged widths, GroupNorm + SiLU in
-padded and compact form, nearest upsample, stride-2 im2col downsample, the one-head attention) and whole decoders / encoders:
-a small 2-level VAE without attention at several aspect ratios, a 3-level VAE with the 512-channel attention, the FLUX.1-dev
-shape at 256^2 and 1024^2 (decode) / 512^2 (encode); bitwise run-to-run determinism; the pipeline call sites.
+Cases: WHOLE decoders / encoders only (the kernels one op at a time, against fp64, are tests/test_vae_kernels_gpu.py): a small 2-level
+VAE without attention at several aspect ratios, a 3-level VAE with the 512-channel attention, the FLUX.1-dev shape at 256^2 and 1024^2
+(decode) / 512^2 (encode); bitwise run-to-run determinism; independence of what the workspace holds on entry; the pipeline call sites.
 """
 import math
 
@@ -102,6 +101,34 @@ def test_encode_vs_oracle_small(dev, cfg_name, H, W):
     lat = hv.encode(x.to(dev).to(BF)).latent_dist.sample(g)
     noise = torch.randn(lat.shape, generator=torch.Generator().manual_seed(9), dtype=BF)
     assert rel_l2(lat, VO.sample_latent(mo.float().cpu(), noise.float())) < 1e-2
+
+
+@torch.no_grad()
+@pytest.mark.parametrize("what,cfg_name,h,w", [("decode", "mid", 8, 8), ("decode", "small", 12, 40), ("encode", "mid", 64, 64)])
+def test_result_does_not_depend_on_workspace_contents(dev, what, cfg_name, h, w):
+    """rf_flux.h calls the workspace caller-owned and asks nothing of its contents: the same call on a zeroed workspace, on one whose every
+    word is ~3.4e38 (byte 0x7F) and on one whose every word is NaN (byte 0xFF) must give bit-equal interiors.  (mid 8x8: the attention;
+    small 12x40: folded convolutions, whose last GEMM row reads past the image, up to conv_out's fold 32 at W + 3 = 99; the encoder.)
+    The input's own slack stays zero, as rf_flux.h requires."""
+    from reflectionflow_amd.flux.vae_hip import HipVAE
+    cfg = SMALL if cfg_name == "small" else MID
+    hv = HipVAE(make_vae(cfg, seed=6).to(dev).to(BF))
+    g = torch.Generator().manual_seed(h * 7 + w)
+    if what == "decode":
+        x = torch.randn(1, 16, h, w, generator=g).to(dev).to(BF)
+        run = lambda: hv.decode(x).sample.clone()
+    else:
+        x = (torch.rand(1, 3, h, w, generator=g) * 2 - 1).to(dev).to(BF)
+        run = lambda: hv.encode_moments(x).clone()
+    base = run()
+    assert len(hv._ws) == 1 and torch.isfinite(base.float()).all()
+    (ws,) = hv._ws.values()
+    for byte in (0x7F, 0xFF):
+        ws.fill_(byte)
+        got = run()
+        torch.cuda.synchronize()
+        assert torch.equal(got, base), (f"{what} {cfg_name} {h}x{w}: workspace filled with byte {byte:#x} changes the result "
+                                        f"({int(torch.isnan(got.float()).sum())} NaN, {int((got != base).sum())} of {got.numel()} elements differ)")
 
 
 @torch.no_grad()
