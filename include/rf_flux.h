@@ -162,6 +162,8 @@ int rf_qk_rmsnorm_rope(void* q, void* k, int32_t heads, int32_t S, int32_t s_pad
  *         tile are stored at position  p(kv) = (kv & ~12) | ((kv & 4) << 1) | ((kv & 8) >> 1)
  *         (bits 2 and 3 swapped) -- the order the PV MFMA consumes them in.
  *   out : [S][heads*128] bf16 (token-major, ready for the out-projection GEMM)
+ *   S < S_pad: rows S .. S_pad of q and k are never read (row indices are clamped to S - 1); the key columns S .. S_pad of the
+ *         last vt tile ARE read and multiplied by p = 0, so they must be finite.  The engine entry points below clear them themselves.
  *   n_main: rows [0,n_main) are text+image tokens, [n_main,S) condition tokens.
  *   mode: 0 = plain; 1 = additive bias `cross_bias` on (main<->cond) blocks (attn.c_factor,
  *         block.py:115-122); 2 = mask (main<->cond) blocks (union_cond_attn=False, block.py:106-114)
@@ -323,8 +325,21 @@ typedef struct rf_flux_dims {
   int32_t _pad;
 } rf_flux_dims;
 
+/* Scratch owned by the caller, 256-byte aligned, >= rf_workspace_bytes(dims) bytes.  The contract:
+ *   - one buffer per geometry (dims) and stream: calls that may overlap on the device must not share one;
+ *   - zero-fill it ONCE before its first use.  Only the 4 KiB stream-K flag page inside needs it (its offset is internal;
+ *     rf_debug_workspace_layout in rf_flux_debug.h reports it): a flag must read 0 before the first launch, and every launch
+ *     leaves the page zero again;
+ *   - after that the library depends on no byte of the buffer between calls: every other region (activations, the pad rows and
+ *     pad key columns of the attention operands, LoRA intermediates, partial tiles, fp8 rows and scales) is written by a call
+ *     before that call reads it, so what an earlier call left there -- finite or not -- never reaches a result;
+ *   - reusing one buffer for another geometry is unsupported: the flag page sits at an offset that depends on the geometry, so a
+ *     buffer last used at another geometry holds activations where this one keeps its flags, and a non-zero flag makes a
+ *     stream-K workgroup wait for a partner that never arrives.  Zero-fill again before such a reuse.
+ * The tower workspaces (rf_t5_encode, rf_clip_text_encode[_opts], rf_clip_vision_encode[_opts]) ask less: those calls zero their
+ * flag page themselves, so no byte of a tower workspace matters on entry.  The VAE's: see rf_vae_workspace_bytes. */
 typedef struct rf_workspace {
-  void* base; int64_t bytes;           /* scratch owned by the caller, 256-byte aligned */
+  void* base; int64_t bytes;
 } rf_workspace;
 
 int64_t rf_workspace_bytes(const rf_flux_dims* dims);
@@ -490,7 +505,9 @@ typedef struct rf_t5_weights {
   const rf_t5_layer* layer;               /* HOST array [layers] */
 } rf_t5_weights;
 int64_t rf_t5_workspace_bytes(const rf_t5_weights* w, int32_t B, int32_t S);
-/* ids [B][S] -> out [B][S][ld_out] bf16 = last hidden state (final norm applied); 1 <= B <= 64 sequences share every GEMM launch */
+/* ids [B][S] -> out [B][S][ld_out] bf16 = last hidden state (final norm applied); 1 <= B <= 64 sequences share every GEMM launch.
+ * ws: one buffer per (B, S) and stream, >= rf_t5_workspace_bytes; its contents on entry do not matter (rf_workspace above): the call
+ * zeroes its flag page and the rows S .. S_pad of every sequence itself. */
 int rf_t5_encode(const rf_t5_weights* w, const int32_t* ids, int32_t B, int32_t S, void* out, int64_t ld_out, const rf_workspace* ws, void* stream);
 
 typedef struct rf_clip_layer {
@@ -512,7 +529,7 @@ typedef struct rf_clip_weights {
 } rf_clip_weights;
 int64_t rf_clip_text_workspace_bytes(const rf_clip_weights* w, int32_t B, int32_t S);
 /* ids [B][S] -> last_hidden [B][S][hidden] (may be NULL) and pooled [B][hidden] (may be NULL) = final-normed row eos_pos[b] of
- * sequence b (eos_pos: HOST array [B]) */
+ * sequence b (eos_pos: HOST array [B]).  ws: one buffer per (B, S) and stream; its contents on entry do not matter (rf_workspace above). */
 int rf_clip_text_encode(const rf_clip_weights* w, const int32_t* ids, int32_t B, int32_t S, const int32_t* eos_pos, void* last_hidden, void* pooled,
                         const rf_workspace* ws, void* stream);
 
@@ -550,7 +567,8 @@ typedef struct rf_clip_vision_weights {
 int rf_clip_preprocess(const void* img, int64_t s_img, int64_t s_row, int64_t s_pix, int64_t s_ch, int32_t B, int32_t H, int32_t W, float a,
                        float b, int32_t size, int32_t patch, void* patches, void* stream);
 int64_t rf_clip_vision_workspace_bytes(const rf_clip_vision_weights* w, int32_t B);
-/* patches [B * (image_size / patch)^2][K_pad] (rf_clip_preprocess) -> image_embeds [B][proj_dim] bf16; 1 <= B <= 64 */
+/* patches [B * (image_size / patch)^2][K_pad] (rf_clip_preprocess) -> image_embeds [B][proj_dim] bf16; 1 <= B <= 64.
+ * ws: one buffer per B and stream; its contents on entry do not matter (rf_workspace above). */
 int rf_clip_vision_encode(const rf_clip_vision_weights* w, const void* patches, int32_t B, void* image_embeds, const rf_workspace* ws, void* stream);
 
 /* ViT-H/14 towers (PickScore, HPSv2, LAION CLIP-H: the same CLIPModel, vision hidden 1280 = 16 heads x 80, hidden_act "gelu").
@@ -578,7 +596,8 @@ int rf_gelu_erf_inplace(void* x, int64_t n, void* stream);
  * S_pad rows (S_pad % 32 == 0, <= 2048): rows of q [.][ldq], k [.][ldk] and out [.][ldo] of sequence z start at z * S_pad, head h in
  * columns 64 h ...; vt [64 heads][ldvt] is V transposed (row = channel, column = key) with sequence z's keys at columns z * S_pad.
  * bias: fp32 [.][S_pad][S_pad] with head stride bias_hs (0 = shared by the heads); it must hold -inf in the key columns >= S and may
- * be NULL only when S == S_pad.  Rows >= S of out are not written; rows / keys >= S of q, k, vt must be finite.
+ * be NULL only when S == S_pad.  Rows >= S of out are not written; rows / keys >= S of q, k, vt must be finite (this call runs on the
+ * CALLER's buffers; the towers, which own theirs, make those rows finite themselves).
  *   head_dim     64; anything else returns RF_ERR_UNSUPPORTED
  *   qi           1 | 4 = 64 | 256 queries per workgroup, 0 = the towers' rule (4 when heads * B * ceil(S_pad / 256) >= 256)
  *   stream_keys  0 = the towers' rule: K and V^T resident in the LDS up to S_pad = 512, streamed through it in 128-key chunks with an

@@ -9,6 +9,7 @@
  *   rf_debug_clock_probe     the shader clock a probed launch saw (rf_gemm_desc.clock_probe / an open profile)
  *   rf_debug_text_attention  one launch of the text / CLIP towers' attention kernels on caller buffers (kernel-level parity tests)
  *   rf_debug_vae_op          one op of the VAE (GroupNorm, 3x3 convolution, upsample, downsample, attention) on caller buffers
+ *   rf_debug_workspace_layout, rf_debug_text_workspace_layout   where the regions of an rf_workspace lie (pure arithmetic, callable without a GPU)
  */
 #ifndef RF_FLUX_DEBUG_H
 #define RF_FLUX_DEBUG_H
@@ -109,6 +110,18 @@ typedef struct rf_vae_op_desc {
   const rf_workspace* ws;
 } rf_vae_op_desc;
 int64_t rf_debug_vae_op(const rf_vae_op_desc* d, void* stream);
+
+/* The regions the engine entry points (rf_double_block_fwd ... rf_flux_denoise_guided) carve out of an rf_workspace of rf_workspace_bytes(dims):
+ * out[2 i] = byte offset, out[2 i + 1] = byte length of region i, in this order (14 pairs; n = the pairs `out` has room for, >= 14):
+ *   0 xn   1 q   2 k   3 vt   4 att   5 hid   6 lt   7 x   8 sk_flags   9 sk_partials   10 xn8   11 a8   12 s_xn   13 s_a
+ * (q, k, vt with their rows / key columns S .. s_pad; length 0 for the four fp8 regions when dims->fp8 == 0).  Regions start on 256-byte
+ * boundaries, so up to 255 unused bytes follow each.  sk_flags is the one region whose contents matter on entry (rf_workspace in rf_flux.h).
+ * Returns the number of pairs or an RF_ERR_* status; launches nothing, changes no state. */
+int rf_debug_workspace_layout(const rf_flux_dims* dims, int64_t* out, int32_t n);
+/* The same for a tower workspace (rf_t5_encode, rf_clip_text_encode[_opts], rf_clip_vision_encode[_opts]) of total_bytes = the answer of
+ * its rf_*_workspace_bytes query: 2 pairs, 0 sk_flags, 1 sk_partials (the scratch of the towers' stream-K / split-K GEMMs, carved last).
+ * The towers zero their flag page themselves on every call. */
+int rf_debug_text_workspace_layout(int64_t total_bytes, int64_t* out, int32_t n);
 
 #ifdef __cplusplus
 }

@@ -293,7 +293,29 @@ _EXTRA_SIGS = {
                "rf_debug_text_attention": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64,
                                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
                # one VAE op on caller buffers; workspace bytes when desc.ws is NULL, else a status
-               "rf_debug_vae_op": (C.c_int64, [C.POINTER(rf_vae_op_desc), _P])}
+               "rf_debug_vae_op": (C.c_int64, [C.POINTER(rf_vae_op_desc), _P]),
+               # (offset, length) pairs of the regions of an engine / a tower workspace
+               "rf_debug_workspace_layout": (C.c_int, [C.POINTER(rf_flux_dims), C.POINTER(C.c_int64), C.c_int32]),
+               "rf_debug_text_workspace_layout": (C.c_int, [C.c_int64, C.POINTER(C.c_int64), C.c_int32])}
+WS_REGIONS = ("xn", "q", "k", "vt", "att", "hid", "lt", "x", "sk_flags", "sk_partials", "xn8", "a8", "s_xn", "s_a")
+
+
+def workspace_layout(dims: "rf_flux_dims") -> dict:
+    """rf_debug_workspace_layout as {region: (byte offset, byte length)}"""
+    out = (C.c_int64 * (2 * len(WS_REGIONS)))()
+    n = load().rf_debug_workspace_layout(C.byref(dims), out, len(WS_REGIONS))
+    if n != len(WS_REGIONS):
+        check(n if n < 0 else -1, "rf_debug_workspace_layout")
+    return {name: (int(out[2 * i]), int(out[2 * i + 1])) for i, name in enumerate(WS_REGIONS)}
+
+
+def text_workspace_layout(total_bytes: int) -> dict:
+    """rf_debug_text_workspace_layout as {region: (byte offset, byte length)}"""
+    out = (C.c_int64 * 4)()
+    n = load().rf_debug_text_workspace_layout(int(total_bytes), out, 2)
+    if n != 2:
+        check(n if n < 0 else -1, "rf_debug_text_workspace_layout")
+    return {"sk_flags": (int(out[0]), int(out[1])), "sk_partials": (int(out[2]), int(out[3]))}
 _lib = None
 
 

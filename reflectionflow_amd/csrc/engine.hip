@@ -11,6 +11,7 @@
 //   HID [S][mlp]      FF hidden / single-block MLP branch
 //   LT  [S][256]      LoRA low-rank intermediates (x . lora_A^T)
 //   SK  fp32          GEMM scratch: stream-K flags + per-CU partial tiles, LoRA split-K partials (64 MiB)
+//                     (the 4 KiB flag page is the ONE region that must be zero before the first call; every launch restores it)
 //   X   [S][D]        residual stream (rf_flux_forward only; rows = txt | img | cond)
 //   XN8 [S][D] fp8, A8 [S][D+mlp] fp8, sXN / sA [S] fp32   cfg5 (dims.fp8): quantised GEMM inputs + their row scales
 //
@@ -112,6 +113,25 @@ static int lora_down(const rf_lora_seg& l, const bf16_t* a0, int64_t lda0, int K
   return rf_gemm_bf16(&d, st);
 }
 
+// The online-softmax attention kernels read whole 64-key V^T tiles; the columns of the keys S .. s_pad of the last tile get p = 0,
+// and 0 * v is 0 only for a finite v.  The QKV epilogue writes the live columns only, so with a ragged S the engine clears the last
+// tile of every head before that GEMM: the workspace's previous contents then never reach a result.  (q and k rows >= S are never
+// read: those kernels clamp their row index to S - 1.)  Nothing is launched when S % 64 == 0.
+__global__ __launch_bounds__(256) void clear_vt_tail_kernel(bf16_t* vt, int64_t head_stride, int64_t tail_off) {
+  u32x4* p = (u32x4*)(vt + (int64_t)blockIdx.x * head_stride + tail_off);
+  const u32x4 z = {0u, 0u, 0u, 0u};
+  for (int i = threadIdx.x; i < 128 * 64 * 2 / 16; i += 256) p[i] = z;
+}
+
+static int clear_vt_pad(bf16_t* VT, int heads, const WsLayout& L, hipStream_t st) {
+  if (L.S == L.s_pad) return RF_OK;
+  const int64_t tiles = L.s_pad / 64;
+  ProfScope prof(RF_KC_ROWOP, (double)heads * 128 * 64 * 2, st);
+  hipLaunchKernelGGL(clear_vt_tail_kernel, dim3(heads), dim3(256), 0, st, VT, tiles * (128 * 64), (tiles - 1) * (128 * 64));
+  RF_LAUNCH_CHECK();
+  return RF_OK;
+}
+
 }  // namespace rf
 
 using namespace rf;
@@ -119,6 +139,22 @@ using namespace rf;
 extern "C" int64_t rf_workspace_bytes(const rf_flux_dims* dims) {
   if (!dims) return RF_ERR_NULL;
   return ws_layout(*dims).total;
+}
+
+// (byte offset, byte length) of every region of ws_layout, in the order rf_flux_debug.h documents; pure arithmetic
+extern "C" int rf_debug_workspace_layout(const rf_flux_dims* dims, int64_t* out, int32_t n) {
+  RF_REQUIRE(dims && out, RF_ERR_NULL, "rf_debug_workspace_layout: NULL pointer");
+  RF_REQUIRE(dims->D > 0 && dims->heads > 0 && dims->mlp > 0 && dims->S_txt >= 0 && dims->S_img > 0 && dims->S_cond >= 0, RF_ERR_SHAPE,
+             "rf_debug_workspace_layout: bad dims");
+  const WsLayout L = ws_layout(*dims);
+  const int64_t SD = (int64_t)L.S * dims->D * 2, HS = (int64_t)dims->heads * L.s_pad * 128 * 2, f8 = dims->fp8 ? 1 : 0;
+  const int64_t r[14][2] = {{L.xn, SD}, {L.q, HS}, {L.k, HS}, {L.vt, HS}, {L.att, SD}, {L.hid, (int64_t)L.S * dims->mlp * 2},
+                            {L.lt, (int64_t)L.S * 256 * 2}, {L.x, SD}, {L.sk, 4096}, {L.sk + 4096, L.sk_bytes - 4096},
+                            {L.xn8, f8 * (SD / 2)}, {L.a8, f8 * (int64_t)L.S * (dims->D + dims->mlp)}, {L.s_xn, f8 * L.S * 4},
+                            {L.s_a, f8 * L.S * 4}};
+  RF_REQUIRE(n >= 14, RF_ERR_SHAPE, "rf_debug_workspace_layout: room for %d pairs, 14 needed", n);
+  for (int i = 0; i < 14; ++i) { out[2 * i] = r[i][0]; out[2 * i + 1] = r[i][1]; }
+  return 14;
 }
 
 // =================================================================================================
@@ -205,6 +241,7 @@ extern "C" int rf_double_block_fwd(const rf_flux_dims* dims, const rf_double_blo
   RF_TRY(ln_mod(1, 0));
 
   // 2. QKV projections, written head-major into the joint [txt|img|cond] attention operands
+  RF_TRY(clear_vt_pad(VT, H, L, st));
   {
     rf_gemm_desc d;
     memset(&d, 0, sizeof(d));
@@ -397,6 +434,7 @@ extern "C" int rf_single_block_fwd(const rf_flux_dims* dims, const rf_single_blo
     RF_TRY(ln_mod_grouped(bf, nbf, ldx, D, D, 1e-6f, st));
   }
   // 2. fused [to_q|to_k|to_v|proj_mlp]: QKV head-major, MLP branch through GELU(tanh) into HID
+  RF_TRY(clear_vt_pad(VT, H, L, st));
   {
     rf_gemm_desc d;
     memset(&d, 0, sizeof(d));

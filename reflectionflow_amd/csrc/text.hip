@@ -596,7 +596,7 @@ int text_ctx(TextCtx& c, const TextSizes& z, int B, int S, int S_pad, const rf_w
   c.ones = (bf16_t*)take(16384 * 2);
   c.sk = take(TEXT_SK); c.sk_bytes = TEXT_SK;
   hipLaunchKernelGGL(fill_bf16_rows_kernel, dim3(64), dim3(256), 0, st, c.ones, (int64_t)16384, 1.0f);
-  RF_CHECK_HIP(hipMemsetAsync(c.sk, 0, 4096, st));                       // stream-K flags
+  RF_CHECK_HIP(hipMemsetAsync(c.sk, 0, 4096, st));                       // stream-K flags: zeroed here on every call, the caller owes nothing
   RF_CHECK_HIP(hipMemsetAsync(c.Xn, 0, (size_t)z.x, st));                // padded rows start finite (zero) and stay finite: they run through
   RF_CHECK_HIP(hipMemsetAsync(c.AO, 0, (size_t)z.ao, st));                // the same norms as real rows; no real row ever reads them (masked keys)
   RF_LAUNCH_CHECK();
@@ -737,6 +737,17 @@ int clip_opts_check(const rf_clip_tower_opts* o, int hidden, int heads, int S_pa
 }  // namespace rf
 
 using namespace rf;
+
+// Where a tower workspace of `total_bytes` (an rf_*_workspace_bytes answer) keeps its GEMM scratch: out = (offset, length) of the
+// stream-K flag page, then of the partial tiles.  text_ctx carves it last and zeroes the flag page itself on every call.
+extern "C" int rf_debug_text_workspace_layout(int64_t total_bytes, int64_t* out, int32_t n) {
+  RF_REQUIRE(out, RF_ERR_NULL, "rf_debug_text_workspace_layout: out NULL");
+  RF_REQUIRE(total_bytes > TEXT_SK && n >= 2, RF_ERR_SHAPE, "rf_debug_text_workspace_layout: total_bytes=%lld n=%d (need a tower's size and room for 2 pairs)",
+             (long long)total_bytes, n);
+  out[0] = total_bytes - TEXT_SK; out[1] = 4096;
+  out[2] = total_bytes - TEXT_SK + 4096; out[3] = TEXT_SK - 4096;
+  return 2;
+}
 
 static int t5_check(const rf_t5_weights* w, int32_t S, const char* who) {
   RF_REQUIRE(w && w->layer && w->embed && w->final_ln, RF_ERR_NULL, "%s: weights NULL", who);

@@ -238,7 +238,8 @@ def get_workspace(device, d: L.rf_flux_dims) -> L.rf_workspace:
             # evict the least recently used workspace; work already enqueued on its stream keeps the memory alive
             # through the caching allocator's stream-ordered reuse (the buffer was allocated on that stream)
             _WS_CACHE.pop(next(iter(_WS_CACHE)))
-        # zero-filled: padded key rows of V^T must be finite (they are multiplied by p = 0)
+        # zero-filled ONCE: the 4 KiB stream-K flag page inside (its offset is internal) must be zero before the first launch; every
+        # launch restores it.  The library depends on no other byte of the buffer between calls (include/rf_flux.h, rf_workspace).
         buf = torch.zeros(n, dtype=torch.uint8, device=device)
     _WS_CACHE[key] = buf          # (re-)insert at the most-recently-used end
     ws = L.rf_workspace()
@@ -315,8 +316,9 @@ class FluxEngine:
              c_factor: Optional[float] = None) -> L.rf_flux_dims:
         return make_dims(self.D, self.heads, self.mlp, S_txt, S_img, S_cond, model_config, c_factor, fp8=self.fp8)
 
-    def workspace(self, d: L.rf_flux_dims) -> L.rf_workspace:
-        return get_workspace(self.device, d)
+    def workspace(self, d: L.rf_flux_dims, ws: Optional[L.rf_workspace] = None) -> L.rf_workspace:
+        """the cached per-(geometry, stream) scratch, or the caller's own `ws` (>= rf_workspace_bytes(d); contract: include/rf_flux.h)"""
+        return get_workspace(self.device, d) if ws is None else ws
 
     def rope_tables(self, txt_ids, img_ids, cond_ids=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """FluxPosEmbed over [txt | img | cond] ids (transformer.py:129-134) -> fp32 [S,128] x2."""
@@ -415,11 +417,12 @@ class FluxEngine:
 
     # ------------------------------------------------------------------ forward / denoise
     def forward(self, latents, ctx, mod_main, cos, sin, cond_latents=None, mod_cond=None, model_config=None,
-                c_factor=None, out=None) -> torch.Tensor:
-        """One sample: latents [S_img, in_ch], ctx [S_txt, joint], mod rows [mod_cols] -> velocity [S_img, in_ch]."""
+                c_factor=None, out=None, ws: Optional[L.rf_workspace] = None) -> torch.Tensor:
+        """One sample: latents [S_img, in_ch], ctx [S_txt, joint], mod rows [mod_cols] -> velocity [S_img, in_ch].
+        ws: the caller's own rf_workspace for this geometry instead of the cached one (forward / denoise / denoise_guided alike)."""
         Sc = 0 if cond_latents is None else cond_latents.shape[0]
         d = self.dims(ctx.shape[0], latents.shape[0], Sc, model_config, c_factor)
-        ws = self.workspace(d)
+        ws = self.workspace(d, ws)
         if out is None:
             out = torch.empty_like(latents)
         for t in (latents, ctx, mod_main, out):
@@ -434,7 +437,7 @@ class FluxEngine:
         return out
 
     def denoise(self, latents, ctx, mod_steps, dts, cos, sin, cond_latents=None, mod_cond=None, model_config=None,
-                c_factor=None, use_graph: Optional[bool] = None) -> torch.Tensor:
+                c_factor=None, use_graph: Optional[bool] = None, ws: Optional[L.rf_workspace] = None) -> torch.Tensor:
         """T-step loop in ONE C call, latents [S_img, in_ch] updated in place.
         mod_steps [T, mod_cols] (row i = modulation table of timestep i), dts = sigma_{i+1}-sigma_i.
         use_graph (default: on for T >= 16 unless RF_DENOISE_GRAPH=0; RF_DENOISE_GRAPH=1 forces it for any T): replay the whole
@@ -444,7 +447,7 @@ class FluxEngine:
         host-side enqueue jitter between the 15 000 launches of a candidate).  Never used while the timing hook is open."""
         Sc = 0 if cond_latents is None else cond_latents.shape[0]
         d = self.dims(ctx.shape[0], latents.shape[0], Sc, model_config, c_factor)
-        ws = self.workspace(d)
+        ws = self.workspace(d, ws)
         T = len(dts)
         if mod_steps.shape != (T, self.mod_cols) or not mod_steps.is_contiguous():
             raise ops.RFError("FluxEngine.denoise: mod_steps must be contiguous [T, mod_cols]")
@@ -462,7 +465,8 @@ class FluxEngine:
         return self._run_loop(key, bufs, 1, launch, use_graph)
 
     def denoise_guided(self, latents, ctx, mod_steps, mod_unc_steps, dts, cos, sin, cond_latents, unc_latents, mod_cond, scale,
-                       model_config=None, c_factor=None, use_graph: Optional[bool] = None) -> torch.Tensor:
+                       model_config=None, c_factor=None, use_graph: Optional[bool] = None,
+                       ws: Optional[L.rf_workspace] = None) -> torch.Tensor:
         """The T-step loop with image guidance (generate.py:250-276) in ONE C call, rf_flux_denoise_guided: per step the conditional
         forward, the unconditional forward (unc_latents [T or 1, S_cond, in_ch]: its condition tokens per step, one set = the same
         every step; mod_unc_steps [T, mod_cols]: its table rows, guidance 1) and the guided Euler step; latents [S_img, in_ch] updated
@@ -471,7 +475,7 @@ class FluxEngine:
         if cond_latents is None or mod_cond is None or unc_latents is None:
             raise ops.RFError("FluxEngine.denoise_guided: image guidance needs a condition (cond_latents, unc_latents, mod_cond)")
         d = self.dims(ctx.shape[0], latents.shape[0], cond_latents.shape[0], model_config, c_factor)
-        ws = self.workspace(d)
+        ws = self.workspace(d, ws)
         T = len(dts)
         for t, what in ((mod_steps, "mod_steps"), (mod_unc_steps, "mod_unc_steps")):
             if t.shape != (T, self.mod_cols) or not t.is_contiguous():

@@ -39,7 +39,7 @@ def test_library_exports_every_declared_symbol(lib):
     # the product ABI carries no timing / debug entry point: those live in rf_flux_debug.h
     assert not [n for n in names if n.startswith(("rf_debug_", "rf_time_", "rf_profile_"))]
     dbg = header_functions(HDR_DEBUG)
-    assert set(dbg) == set(_lib.debug_symbols()) and len(dbg) == 12
+    assert set(dbg) == set(_lib.debug_symbols()) and len(dbg) == 14
     for n in dbg:
         assert hasattr(raw, n), f"librf_flux.so does not export {n} (declared in include/rf_flux_debug.h)"
     assert lib.rf_abi_version() == _lib.ABI_VERSION and lib.rf_target_arch() == 950
@@ -80,7 +80,8 @@ def test_no_kernel_selecting_switch_is_exported(lib):
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     dbg = sorted(set(re.findall(r"\b(rf_debug_[a-z0-9_]+)", out)))
     assert dbg == ["rf_debug_attn_mix_plan", "rf_debug_clock_probe", "rf_debug_last_attn_bwd_path", "rf_debug_last_attn_path",
-                   "rf_debug_last_gemm_path", "rf_debug_sk_plan", "rf_debug_text_attention", "rf_debug_vae_op"], dbg
+                   "rf_debug_last_gemm_path", "rf_debug_sk_plan", "rf_debug_text_attention", "rf_debug_text_workspace_layout", "rf_debug_vae_op",
+                   "rf_debug_workspace_layout"], dbg
     d = _lib.rf_gemm_desc()
     d.N, d.num_groups, d.schedule = 64, 1, 17
     assert lib.rf_gemm_bf16(C.byref(d), None) == -1 and b"schedule=17" in lib.rf_last_error()
