@@ -38,7 +38,9 @@ const char* rf_last_error(void);
 /* ABI version: bump on any struct/signature change (v13: rf_attn_bwd_desc.kernel, rf_lora_adamw / rf_lora_prodigy; v14: rf_lora_fuse /
  * rf_lora_unfuse_grads, rf_qkv_train_fwd's forward-only form; v15: rf_lora_clip_grad_norm; v16: the CLIP-score verifier,
  * rf_clip_vision_weights / rf_clip_preprocess / rf_clip_vision_encode / rf_clip_score; v17: the search's on-device round hand-off,
- * rf_image_levels / rf_pil_resize_to_vae_input). */
+ * rf_image_levels / rf_pil_resize_to_vae_input).  Additive changes keep the number: new entry points, and fields APPENDED to a
+ * descriptor that every call accepted so far never reads (rf_attn_bwd_desc.n_main / cross_bias: read for mode != 0 only, which v17
+ * refused). */
 int rf_abi_version(void);
 /* Returns 950 when the library was compiled for gfx950. */
 int rf_target_arch(void);
@@ -670,7 +672,10 @@ int rf_qkv_train_bwd(const void* raw, int64_t ld_raw, int32_t heads, int32_t S, 
                      const float* cos_tab, const float* sin_tab, float eps, float q_scale,
                      const void* dq, const void* dk, const void* dv, void* d_raw, int64_t ld_draw, void* stream);
 
-/* Flash-attention backward (F.scaled_dot_product_attention of block.py:123-125), plain joint attention (mode 0):
+/* Flash-attention backward (F.scaled_dot_product_attention of block.py:123-125) in the three modes of rf_attention: 0 = plain joint
+ * attention, 1 = `cross_bias` added to the scores of the (main <-> condition) pairs (attn.c_factor, block.py:115-122), 2 = those pairs
+ * masked (union_cond_attn: false, block.py:106-114).  A pair (query, key) is cross iff exactly one of the two rows is >= n_main.  With
+ * lse_given the statistics are rf_attn_desc.lse of a forward in the SAME mode (the statistic of the biased / masked scores).
  *   q (scaled), k, v, qt, kt from rf_qkv_train_fwd;  o = the forward's output, dout = its gradient, both [S][ld] token-major;
  *   dq, dk, dv: [heads][s_pad][128] bf16;  dot ([heads][s_pad/32][128][32] bf16), lse, dsum (fp32 [heads][s_pad]): scratch.
  * Three launches: D = rowsum(dO o O) + dO^T tiles; per 64 queries the row statistics then dq; per 128 keys dk, dv. */
@@ -692,7 +697,13 @@ typedef struct rf_attn_bwd_desc {
   int32_t lse_given;   /* 1: lse[heads][s_pad] holds the forward's row statistics for rows < S (rf_attn_desc.lse of the SAME q, k): the
                           dq kernel skips its own statistics pass over the keys (a quarter of its work).  0: lse is scratch. */
   int32_t kernel;      /* rf_attn_bwd_kernel: RF_ATTN_BWD_AUTO, or one dq form | one dK / dV form.  Every form gives the same gradients to
-                          rounding; the forms differ in queries / keys per workgroup, i.e. in how a (heads, S) fills the CUs. */
+                          rounding; the forms differ in queries / keys per workgroup, i.e. in how a (heads, S) fills the CUs.
+                          RF_ATTN_BWD_DKV_128X2 exists for mode 0 only (AUTO never picks it otherwise; asking for it is
+                          RF_ERR_UNSUPPORTED). */
+  /* appended (additive to ABI v17: the offsets above did not move); read for mode != 0 only, which was RF_ERR_UNSUPPORTED before */
+  int32_t n_main;      /* modes 1 / 2: rows [0, n_main) are text + image tokens, [n_main, S) condition tokens; 0 < n_main < S (any value:
+                          no tile size divides it) */
+  float cross_bias;    /* mode 1: log(c_factor), added to the scores of the (main <-> condition) pairs -- rf_attn_desc.cross_bias */
 } rf_attn_bwd_desc;
 int rf_attention_bwd(const rf_attn_bwd_desc* d, void* stream);
 
@@ -751,8 +762,8 @@ int rf_lora_fuse(const rf_lora_fuse_entry* entries, int32_t n_entries, int32_t K
 int rf_lora_unfuse_grads(const rf_lora_fuse_entry* entries, int32_t n_entries, int32_t K, int32_t N, int32_t r_pad, const void* dA,
                          const void* dBs, int32_t accumulate, void* stream);
 
-/* Optimizer update of the LoRA factors (train_flux/train/model.py:105-117: torch.optim.AdamW or prodigyopt.Prodigy over the LoRA
- * parameters; config.yaml:55-61 ships Prodigy lr 1, use_bias_correction, safeguard_warmup, weight_decay 0.01) over ONE flat bucket:
+/* Optimizer update of the LoRA factors (train_flux/train/model.py:105-117: torch.optim.AdamW, prodigyopt.Prodigy or torch.optim.SGD over the
+ * LoRA parameters; config.yaml:55-61 ships Prodigy lr 1, use_bias_correction, safeguard_warmup, weight_decay 0.01) over ONE flat bucket:
  *   param, grad : bf16 [n] (every LoRA factor / its gradient is a view into them; n % 8 == 0);
  *   exp_avg, exp_avg_sq (, s) : bf16 [n] (what torch / prodigyopt keep for bf16 parameters) or fp32 [n] when state_fp32;
  *   grad_scale  : multiplies every gradient on the way in (1 / world_size behind a SUM all-reduce: the averaging pass is fused away).
@@ -765,6 +776,12 @@ int rf_lora_unfuse_grads(const rf_lora_fuse_entry* entries, int32_t n_entries, i
  * beta3 <= 0 means sqrt(beta2).  Three launches: moments + partial sums, the new d (one workgroup), the parameter update. */
 int rf_lora_adamw(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, int32_t state_fp32, int32_t step,
                   float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* stream);
+/* rf_lora_sgd = one step of torch.optim.SGD (additive to ABI v17; the third optimizer of train_flux/train/model.py:107-117): g = grad_scale * grad,
+ * negated when `maximize`; g += weight_decay * p; buf = g on step 1, momentum * buf + (1 - dampening) * g afterwards; g = g + momentum * buf
+ * (nesterov) or buf; p -= lr * g.  Each of these is rounded to bf16 where torch's tensor ops on bf16 tensors round (the buffer's only
+ * when it is bf16).  momentum_buffer: bf16 [n], or fp32 [n] when state_fp32; untouched when momentum == 0.  `step` is 1-based. */
+int rf_lora_sgd(void* param, const void* grad, void* momentum_buffer, int64_t n, int32_t state_fp32, int32_t step, float lr, float momentum,
+                float dampening, float weight_decay, int32_t nesterov, int32_t maximize, float grad_scale, void* stream);
 int64_t rf_lora_prodigy_partials_bytes(int64_t n);
 int rf_lora_prodigy(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, void* s, const void* p0, int64_t n,
                     int32_t state_fp32, double* dstate, float lr, float beta1, float beta2, float beta3, float eps,

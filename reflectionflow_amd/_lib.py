@@ -60,7 +60,8 @@ class rf_attn_desc(C.Structure):
 class rf_attn_bwd_desc(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("q", "k", "v", "qt", "kt", "o", "dout")] + [("ldo", C.c_int64), ("lddo", C.c_int64)] + [
         (n, C.c_void_p) for n in ("dq", "dk", "dv", "dot", "lse", "dsum")] + [
-        ("heads", C.c_int32), ("S", C.c_int32), ("s_pad", C.c_int32), ("mode", C.c_int32), ("lse_given", C.c_int32), ("kernel", C.c_int32)]
+        ("heads", C.c_int32), ("S", C.c_int32), ("s_pad", C.c_int32), ("mode", C.c_int32), ("lse_given", C.c_int32), ("kernel", C.c_int32),
+        ("n_main", C.c_int32), ("cross_bias", C.c_float)]                       # appended within ABI v17 (additive); mode 0 reads neither
 
 
 class rf_lora_fuse_entry(C.Structure):
@@ -273,6 +274,7 @@ _SIGS = {
     "rf_gemm_tn_skinny": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "rf_lora_adamw": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "rf_lora_prodigy_partials_bytes": (C.c_int64, [C.c_int64]),
+    "rf_lora_sgd": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, _P]),
     "rf_lora_clip_grad_norm": (C.c_int, [_P, C.c_int64, C.c_float, C.c_float, _P, C.c_int64, _P, _P]),
     "rf_lora_prodigy": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P] + [C.c_float] * 6 + [C.c_int32] * 3 + [C.c_float] * 3 +
                         [_P, C.c_int64, _P]),

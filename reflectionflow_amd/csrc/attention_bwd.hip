@@ -20,6 +20,8 @@
 // (rf_qkv_train_fwd for q~ / k, attn_bwd_prep_kernel for dO), so every LDS stage here is a straight 16-byte copy and every
 // fragment read a conflict-free ds_read_b128: row-major [32][128] tiles are XOR-swizzled per 16-byte chunk (chunk ^ (row & 15)),
 // transposed tiles are read as 1 KiB contiguous per fragment.
+#include <cmath>
+
 #include "common.hpp"
 
 namespace rf {
@@ -176,6 +178,20 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const bf16_t* __rest
   }
 }
 
+// ---- the condition modes of the forward (attention.hip, block.py:106-122) ------------------------------------------------------
+// Rows [0, n_main) are text + image tokens, [n_main, S) condition tokens; a (query, key) pair is CROSS iff exactly one of the two is
+// a condition token.  MODE 1 adds bias2 = log2(e) * cross_bias to the cross scores, MODE 2 gives the cross pairs P = 0.  Both kernels
+// below run the loops of mode 0 unchanged -- same steps, barriers and ring traffic, no step is skipped: a step whose pairs are all
+// cross contributes exact zeros -- and decide per ELEMENT, so n_main need not be a multiple of any tile.  The kernels take the two
+// values as a trailing argument pack that is EMPTY for MODE 0: the mode-0 instantiations keep the kernel arguments, and with them the
+// code, they had before the modes existed (profiles/attention_bwd_modes.md).
+struct CrossArgs {
+  int n_main;
+  float bias2;
+};
+__device__ __forceinline__ CrossArgs cross_args() { return CrossArgs{0, 0.f}; }
+__device__ __forceinline__ CrossArgs cross_args(const CrossArgs c) { return c; }
+
 // (head, row block) of a workgroup of the (blocks, heads) grids below.  Workgroup L = blockIdx.y * gridDim.x + blockIdx.x is placed on
 // XCD L % 8; taken literally that spreads the ~25 workgroups of a head over all eight L2s and each of them fetches the head's
 // K / V (Q / dO) stream for itself -- rocprofv3 FETCH_SIZE: 944 MB per dq launch for 104 MB of distinct operands.  With
@@ -199,11 +215,13 @@ __device__ __forceinline__ void head_and_block(int& head, int& blk) {
 // HAVE_LSE: the forward launch already wrote the row statistics (rf_attn_desc.lse): pass 1 is skipped.
 // NW waves (8 or 4) x QT query tiles: 16 NW QT queries per workgroup -- the host picks the pair whose grid wastes least of its last
 // round of CUs (S = 5632 x 24 heads: 256-query workgroups are 2.06 rounds run as 3, 192-query ones 2.81).
-template <int QT, bool HAVE_LSE, int NW>
+template <int QT, bool HAVE_LSE, int NW, int MODE = 0, typename... MA>
 __global__ __launch_bounds__(NW * 64) void attn_bwd_dq_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                           const bf16_t* __restrict__ v, const bf16_t* __restrict__ kt,
                                                           const bf16_t* __restrict__ dout, int64_t lddo, const float* __restrict__ dsum,
-                                                          float* __restrict__ lse, bf16_t* __restrict__ dq, int S, int s_pad) {
+                                                          float* __restrict__ lse, bf16_t* __restrict__ dq, int S, int s_pad, MA... ma) {
+  static_assert(sizeof...(MA) == (MODE != 0 ? 1 : 0), "MODE != 0 takes one CrossArgs, mode 0 nothing");
+  const CrossArgs ca = cross_args(ma...);
   extern __shared__ __attribute__((aligned(16))) char smem[];     // AB_RING stages of {K rows | V rows | K^T tile} (98 304 bytes)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, g = lane >> 4;
   int head, blk;
@@ -225,6 +243,12 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dq_kernel(const bf16_t* __re
   }
   const int nsteps = (S + 31) >> 5;
   const float NEG = -__builtin_huge_valf();
+  // MODE != 0: element r of score tile t2 of step st is (key st * 32 + 16 t2 + 4 g + r, query qrow[t]); cross iff one is a condition row
+  bool qcond[QT];
+  if constexpr (MODE != 0) {
+#pragma unroll
+    for (int t = 0; t < QT; ++t) qcond[t] = qrow[t] >= ca.n_main;
+  }
 
   u32x4 rk[8 / NW];
   float my_lse[QT], my_d[QT];
@@ -268,6 +292,13 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dq_kernel(const bf16_t* __re
       for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
+          if constexpr (MODE != 0) {
+            // a masked pair becomes -inf like a key >= S: it leaves (m, l) as they were (exp2(-inf - mx) = 0 with mx finite, and a
+            // lane that has seen nothing but masked pairs skips the update below)
+            const bool cross = (st * 32 + 16 * t2 + 4 * g + r >= ca.n_main) != qcond[t];
+            if (MODE == 1) s[t2][r] += cross ? ca.bias2 : 0.f;
+            else if (cross) s[t2][r] = NEG;
+          }
           if (st * 32 + 16 * t2 + 4 * g + r >= S) s[t2][r] = NEG;
           mx = fmaxf(mx, s[t2][r]);
         }
@@ -352,9 +383,15 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dq_kernel(const bf16_t* __re
         float gv[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
+          bool cross = false;
+          if constexpr (MODE != 0) cross = (st * 32 + 16 * t2 + 4 * g + r >= ca.n_main) != qcond[t];
+          if constexpr (MODE == 1) s[r] += cross ? ca.bias2 : 0.f;
           float p = __builtin_amdgcn_exp2f(s[r]);
           if (LAST && st * 32 + 16 * t2 + 4 * g + r >= S) p = 0.f;
           gv[r] = p * dp[r];
+          // masked pairs: a select AFTER the exp2 (its argument is the score minus the statistic of the UNMASKED keys: any value,
+          // +inf after the exp2 included), so g is an exact zero whatever the pair's score
+          if constexpr (MODE == 2) gv[r] = cross ? 0.f : gv[r];
         }
         gw[t][2 * t2] = pack2(gv[0], gv[1]);            // slots 4 t2 .. 4 t2 + 3 of this lane group
         gw[t][2 * t2 + 1] = pack2(gv[2], gv[3]);
@@ -400,12 +437,14 @@ __global__ __launch_bounds__(NW * 64) void attn_bwd_dq_kernel(const bf16_t* __re
 // grid (s_pad / (64 KT), heads), 256 threads; a wave owns KT tiles of 16 keys (their k, v fragments stay in registers).
 // LDS per step of 32 queries: q~ rows | dO rows | q~^T tile | dO^T tile | lse[32] | D[32].
 // RING = LDS ring slots, WPE = waves per SIMD the register budget must allow (2: two workgroups share a CU)
-template <int KT, int RING = AB_RING, int WPE = 1>
+template <int KT, int RING = AB_RING, int WPE = 1, int MODE = 0, typename... MA>
 __global__ __launch_bounds__(256, WPE) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ qt,
                                                            const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                            const bf16_t* __restrict__ dout, int64_t lddo, const bf16_t* __restrict__ dot,
                                                            const float* __restrict__ lse, const float* __restrict__ dsum,
-                                                           bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int S, int s_pad) {
+                                                           bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int S, int s_pad, MA... ma) {
+  static_assert(sizeof...(MA) == (MODE != 0 ? 1 : 0), "MODE != 0 takes one CrossArgs, mode 0 nothing");
+  const CrossArgs ca = cross_args(ma...);
   constexpr int BUF = 4 * AB_ROWS + 512;                 // q~ rows | dO rows | q~^T tile | dO^T tile | lse2[64] | D[64]
   extern __shared__ __attribute__((aligned(16))) char smem[];   // RING * BUF = 133 120 bytes (dynamic)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l15 = lane & 15, g = lane >> 4;
@@ -430,6 +469,12 @@ __global__ __launch_bounds__(256, WPE) void attn_bwd_dkv_kernel(const bf16_t* __
 #pragma unroll
     for (int dt = 0; dt < 8; ++dt) akv[kt_][dt] = f32x4{0.f, 0.f, 0.f, 0.f}, avv[kt_][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nsteps = (S + 31) >> 5;
+  // MODE != 0: element r of score tile (t, kt_) of step st is (query st * 32 + 16 t + 4 g + r, key kv0 + 16 kt_ + l15)
+  bool kcond[KT];
+  if constexpr (MODE != 0) {
+#pragma unroll
+    for (int kt_ = 0; kt_ < KT; ++kt_) kcond[kt_] = kv0 + 16 * kt_ + l15 >= ca.n_main;
+  }
   // stage = q~ rows | dO rows | q~^T tile | dO^T tile | lse2[64] | D[64] (the kernel uses the first 32 of each)
   const rsrc_t r_q = RF_MAKE_RSRC_N(q, (int64_t)gridDim.y * s_pad * 256), r_qt = RF_MAKE_RSRC_N(qt, (int64_t)gridDim.y * s_pad * 256);
   const rsrc_t r_dot = RF_MAKE_RSRC_N(dot, (int64_t)gridDim.y * s_pad * 256);
@@ -487,8 +532,13 @@ __global__ __launch_bounds__(256, WPE) void attn_bwd_dkv_kernel(const bf16_t* __
         float pv[4], gv[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
+          bool cross = false;
+          if constexpr (MODE != 0) cross = (st * 32 + 16 * t + 4 * g + r >= ca.n_main) != kcond[kt_];
+          if constexpr (MODE == 1) s[r] += cross ? ca.bias2 : 0.f;
           pv[r] = __builtin_amdgcn_exp2f(s[r]);                              // padded queries: -lse = -1e30 -> 0
+          if constexpr (MODE == 2) pv[r] = cross ? 0.f : pv[r];              // (a select after the exp2, as in the dq kernel)
           gv[r] = pv[r] * dp[r];                                             // g / ln 2 (ln 2 goes onto the finished dK)
+          if constexpr (MODE == 2) gv[r] = cross ? 0.f : gv[r];
         }
         pw[kt_][2 * t] = pack2(pv[0], pv[1]), pw[kt_][2 * t + 1] = pack2(pv[2], pv[3]);     // slots 4 t .. 4 t + 3 of this lane group
         gw[kt_][2 * t] = pack2(gv[0], gv[1]), gw[kt_][2 * t + 1] = pack2(gv[2], gv[3]);
@@ -545,13 +595,26 @@ extern "C" int rf_attention_bwd(const rf_attn_bwd_desc* d, void* stream) {
              RF_ERR_NULL, "rf_attention_bwd: NULL operand");
   RF_REQUIRE(d->heads > 0 && d->S > 0 && d->s_pad >= d->S && d->s_pad % 64 == 0, RF_ERR_SHAPE,
              "rf_attention_bwd: heads=%d S=%d s_pad=%d (need s_pad %% 64 == 0, s_pad >= S)", d->heads, d->S, d->s_pad);
-  RF_REQUIRE(d->mode == 0, RF_ERR_UNSUPPORTED, "rf_attention_bwd: only the plain joint attention (mode 0) has a backward");
+  RF_REQUIRE(d->mode >= 0 && d->mode <= 2, RF_ERR_UNSUPPORTED,
+             "rf_attention_bwd: mode=%d is not 0 (plain), 1 (cross bias) or 2 (cross blocks masked)", d->mode);
+  // modes 1 / 2: both regions non-empty, so every row keeps at least one unmasked key
+  RF_REQUIRE(d->mode == 0 || (d->n_main > 0 && d->n_main < d->S), RF_ERR_SHAPE,
+             "rf_attention_bwd: mode %d needs 0 < n_main < S (n_main=%d S=%d)", d->mode, d->n_main, d->S);
+  RF_REQUIRE(d->mode == 0 || std::isfinite(d->cross_bias), RF_ERR_SHAPE, "rf_attention_bwd: cross_bias must be finite");
   RF_REQUIRE(d->ldo % 8 == 0 && d->lddo % 8 == 0 && aligned16(d->o) && aligned16(d->dout) && aligned16(d->q) && aligned16(d->k) &&
                  aligned16(d->v) && aligned16(d->qt) && aligned16(d->kt) && aligned16(d->dot) && aligned16(d->dq) && aligned16(d->dk) &&
                  aligned16(d->dv),
              RF_ERR_ALIGN, "rf_attention_bwd: operands must be 16-byte aligned with row pitches %% 8 == 0");
+  int dq_form = d->kernel & 0xff, dkv_form = d->kernel & 0xff00;
+  RF_REQUIRE((d->kernel & ~0xffff) == 0 && dq_form <= RF_ATTN_BWD_DQ_192 && dkv_form <= RF_ATTN_BWD_DKV_128X2, RF_ERR_UNSUPPORTED,
+             "rf_attention_bwd: kernel=0x%x is not an rf_attn_bwd_kernel combination", d->kernel);
+  // the two-workgroups-per-CU dK / dV form has no register to spare for the region tests (it already keeps 12 dwords in scratch in
+  // mode 0): modes 1 / 2 run the one-per-CU forms
+  RF_REQUIRE(d->mode == 0 || dkv_form != RF_ATTN_BWD_DKV_128X2, RF_ERR_UNSUPPORTED,
+             "rf_attention_bwd: RF_ATTN_BWD_DKV_128X2 exists for mode 0 only (mode=%d)", d->mode);
   hipStream_t st = (hipStream_t)stream;
   const int S = d->S, sp = d->s_pad, H = d->heads;
+  const CrossArgs ca{d->n_main, d->cross_bias * 1.4426950408889634f};
   // algorithmic work = the 5 products of a flash backward (S, dP, dV, dK, dq~) x 2 S^2 128 per head = 2.5 x the forward's;
   // this two-kernel, atomics-free form EXECUTES 8 (S three times: statistics, dq~ pass, dK / dV pass; dP twice), 7 when the
   // forward supplied the row statistics (lse_given)
@@ -583,10 +646,33 @@ extern "C" int rf_attention_bwd(const rf_attn_bwd_desc* d, void* stream) {
     RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<2, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS / 2));
     attr_set = true;
   }
+  static bool attr_set_modes = false;
+  if (d->mode != 0 && !attr_set_modes) {
+#define RF_DQ_ATTR(QT_, NW_)                                                                                                                 \
+  RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<QT_, true, NW_, 1, CrossArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ_LDS));  \
+  RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<QT_, false, NW_, 1, CrossArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ_LDS)); \
+  RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<QT_, true, NW_, 2, CrossArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ_LDS));  \
+  RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<QT_, false, NW_, 2, CrossArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ_LDS));
+    RF_DQ_ALL(RF_DQ_ATTR)
+#undef RF_DQ_ATTR
+    RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<2, AB_RING, 1, 1, CrossArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS));
+    RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<2, AB_RING, 1, 2, CrossArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS));
+    RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<3, AB_RING, 1, 1, CrossArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS));
+    RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<3, AB_RING, 1, 2, CrossArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS));
+    attr_set_modes = true;
+  }
+#define RF_DQ_LAUNCH_MODE(QT_, NW_, LSE_, MODE_)                                                                                        \
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<QT_, LSE_, NW_, MODE_, CrossArgs>), grid, dim3(NW_ * 64), DQ_LDS, st, (const bf16_t*)d->q,     \
+                     (const bf16_t*)d->k, (const bf16_t*)d->v, (const bf16_t*)d->kt, (const bf16_t*)d->dout, d->lddo,                   \
+                     (const float*)d->dsum, d->lse, (bf16_t*)d->dq, S, sp, ca)
 #define RF_DQ_LAUNCH(QT_, NW_)                                                                                                          \
   {                                                                                                                                     \
     const dim3 grid((sp + 16 * NW_ * QT_ - 1) / (16 * NW_ * QT_), H);                                                                   \
-    if (d->lse_given)                                                                                                                   \
+    if (d->mode == 1 && d->lse_given) RF_DQ_LAUNCH_MODE(QT_, NW_, true, 1);                                                             \
+    else if (d->mode == 1) RF_DQ_LAUNCH_MODE(QT_, NW_, false, 1);                                                                       \
+    else if (d->mode == 2 && d->lse_given) RF_DQ_LAUNCH_MODE(QT_, NW_, true, 2);                                                        \
+    else if (d->mode == 2) RF_DQ_LAUNCH_MODE(QT_, NW_, false, 2);                                                                       \
+    else if (d->lse_given)                                                                                                               \
       hipLaunchKernelGGL((attn_bwd_dq_kernel<QT_, true, NW_>), grid, dim3(NW_ * 64), DQ_LDS, st, (const bf16_t*)d->q,                  \
                          (const bf16_t*)d->k, (const bf16_t*)d->v, (const bf16_t*)d->kt, (const bf16_t*)d->dout, d->lddo,               \
                          (const float*)d->dsum, d->lse, (bf16_t*)d->dq, S, sp);                                                        \
@@ -595,9 +681,6 @@ extern "C" int rf_attention_bwd(const rf_attn_bwd_desc* d, void* stream) {
                          (const bf16_t*)d->k, (const bf16_t*)d->v, (const bf16_t*)d->kt, (const bf16_t*)d->dout, d->lddo,               \
                          (const float*)d->dsum, d->lse, (bf16_t*)d->dq, S, sp);                                                        \
   }
-  int dq_form = d->kernel & 0xff, dkv_form = d->kernel & 0xff00;
-  RF_REQUIRE((d->kernel & ~0xffff) == 0 && dq_form <= RF_ATTN_BWD_DQ_192 && dkv_form <= RF_ATTN_BWD_DKV_128X2, RF_ERR_UNSUPPORTED,
-             "rf_attention_bwd: kernel=0x%x is not an rf_attn_bwd_kernel combination", d->kernel);
   if (dq_form == RF_ATTN_BWD_AUTO) {
     const int64_t c256 = cost(256), c192 = cost(192), c128 = cost(128);
     dq_form = (c192 < c256 && c192 <= c128) ? RF_ATTN_BWD_DQ_192 : c128 < c256 ? RF_ATTN_BWD_DQ_128 : RF_ATTN_BWD_DQ_256;
@@ -606,6 +689,7 @@ extern "C" int rf_attention_bwd(const rf_attn_bwd_desc* d, void* stream) {
   else if (dq_form == RF_ATTN_BWD_DQ_128) RF_DQ_LAUNCH(2, 4)
   else RF_DQ_LAUNCH(2, 8)
 #undef RF_DQ_LAUNCH
+#undef RF_DQ_LAUNCH_MODE
 #undef RF_DQ_ALL
   RF_LAUNCH_CHECK();
 #define RF_DKV_LAUNCH(KERNEL, KT_, LDS_)                                                                                                  \
@@ -619,14 +703,25 @@ extern "C" int rf_attention_bwd(const rf_attn_bwd_desc* d, void* stream) {
     if (dkv_form == RF_ATTN_BWD_AUTO) {
       const int64_t wg128 = (int64_t)((sp + 127) / 128) * H;
       const int64_t c2 = ((wg128 + 2 * num_cus - 1) / (2 * num_cus)) * 226;   // 128 rows x 1.77
-      dkv_form = (c2 < cost(128) && c2 < cost(192)) ? RF_ATTN_BWD_DKV_128X2 : cost(128) < cost(192) ? RF_ATTN_BWD_DKV_128 : RF_ATTN_BWD_DKV_192;
+      dkv_form = (d->mode == 0 && c2 < cost(128) && c2 < cost(192)) ? RF_ATTN_BWD_DKV_128X2
+                 : cost(128) < cost(192)                            ? RF_ATTN_BWD_DKV_128
+                                                                    : RF_ATTN_BWD_DKV_192;
     }
-    if (dkv_form == RF_ATTN_BWD_DKV_128X2) RF_DKV_LAUNCH((attn_bwd_dkv_kernel<2, 2, 2>), 2, DKV_LDS / 2);
+#define RF_DKV_LAUNCH_MODE(KT_, MODE_)                                                                                                    \
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<KT_, AB_RING, 1, MODE_, CrossArgs>), dim3((sp + 64 * KT_ - 1) / (64 * KT_), H), dim3(256), DKV_LDS, \
+                     st, (const bf16_t*)d->q, (const bf16_t*)d->qt, (const bf16_t*)d->k, (const bf16_t*)d->v, (const bf16_t*)d->dout,    \
+                     d->lddo, (const bf16_t*)d->dot, (const float*)d->lse, (const float*)d->dsum, (bf16_t*)d->dk, (bf16_t*)d->dv, S, sp, ca)
+    if (d->mode == 1 && dkv_form == RF_ATTN_BWD_DKV_128) RF_DKV_LAUNCH_MODE(2, 1);
+    else if (d->mode == 1) RF_DKV_LAUNCH_MODE(3, 1);
+    else if (d->mode == 2 && dkv_form == RF_ATTN_BWD_DKV_128) RF_DKV_LAUNCH_MODE(2, 2);
+    else if (d->mode == 2) RF_DKV_LAUNCH_MODE(3, 2);
+    else if (dkv_form == RF_ATTN_BWD_DKV_128X2) RF_DKV_LAUNCH((attn_bwd_dkv_kernel<2, 2, 2>), 2, DKV_LDS / 2);
     else if (dkv_form == RF_ATTN_BWD_DKV_128) RF_DKV_LAUNCH((attn_bwd_dkv_kernel<2>), 2, DKV_LDS);
     else RF_DKV_LAUNCH((attn_bwd_dkv_kernel<3>), 3, DKV_LDS);
   }
   g_last_attn_bwd_path = dq_form | dkv_form;
 #undef RF_DKV_LAUNCH
+#undef RF_DKV_LAUNCH_MODE
   RF_LAUNCH_CHECK();
   return RF_OK;
 }

@@ -8,6 +8,7 @@
 // foreach over 354 tensors.  All of it is HBM-bound streaming: 16-byte accesses, fp32 arithmetic, one rounding per stored value.
 //
 //   rf_lora_adamw    torch.optim.AdamW's update (decoupled decay, bias correction, no amsgrad), element for element
+//   rf_lora_sgd      torch.optim.SGD's update (momentum, dampening, nesterov, weight decay, maximize), rounding for rounding
 //   rf_lora_prodigy  Prodigy (Mishchenko & Defazio 2023, "Prodigy: An Expeditiously Adaptive Parameter-Free Learner", Algorithm 4 =
 //                    the Adam form; option names and defaults of the `prodigyopt` package, which is NOT in this image: parity
 //                    unpinned, see oracle/optim_oracle.py).  The distance estimate d lives on the DEVICE (`dstate`): the two global
@@ -87,6 +88,49 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(bf16_t* __restrict__
     store_bf8(param, i, p);
     StateIO<F32>::store(exp_avg, i, m);
     StateIO<F32>::store(exp_avg_sq, i, v);
+  }
+}
+
+// ---- SGD ---------------------------------------------------------------------------------------------------------------------
+// torch.optim.SGD (torch/optim/sgd.py::_single_tensor_sgd), the reference's third optimizer (train_flux/train/model.py:107-117):
+//   g = maximize ? -g : g;  g += wd p;  buf = first step ? g : mu buf + (1 - dampening) g;  g = nesterov ? g + mu buf : buf;  p -= lr g
+// Every line of that is one tensor op on bf16 tensors, i.e. an fp32 result ROUNDED to bf16; the kernel rounds at the same places (the
+// buffer's two ops only when it is kept in bf16), so it follows torch through cancellations (mu buf + (1 - dampening) g near zero)
+// where one rounding at the end would be many bf16 spacings away.
+struct SgdScalars {
+  float lr, momentum, one_minus_dampening, weight_decay, grad_scale;
+  int nesterov, maximize, first;
+};
+
+__device__ __forceinline__ float round_bf(const float x) { return bf2f(f2bf(x)); }
+
+template <bool F32>
+__global__ __launch_bounds__(OPT_THREADS) void sgd_kernel(bf16_t* __restrict__ param, const bf16_t* __restrict__ grad, void* __restrict__ buf,
+                                                          int64_t n, SgdScalars c) {
+  const int64_t base = (int64_t)blockIdx.x * OPT_BLOCK_ELEMS + threadIdx.x * OPT_VEC;
+#pragma unroll
+  for (int it = 0; it < OPT_ITEMS; ++it) {
+    const int64_t i = base + (int64_t)it * OPT_THREADS * OPT_VEC;
+    if (i >= n) break;                                    // n % 8 == 0: an access is all in or all out
+    float p[8], g[8], m[8];
+    load_bf8(param, i, p);
+    load_bf8(grad, i, g);
+    if (c.momentum != 0.f && !c.first) StateIO<F32>::load(buf, i, m);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float gj = g[j] * c.grad_scale;
+      if (c.maximize) gj = -gj;
+      if (c.weight_decay != 0.f) gj = round_bf(gj + c.weight_decay * p[j]);
+      if (c.momentum != 0.f) {
+        if (c.first) m[j] = gj;
+        else if (F32) m[j] = m[j] * c.momentum + c.one_minus_dampening * gj;
+        else m[j] = round_bf(round_bf(m[j] * c.momentum) + c.one_minus_dampening * gj);
+        gj = c.nesterov ? round_bf(gj + c.momentum * m[j]) : m[j];
+      }
+      p[j] -= c.lr * gj;
+    }
+    store_bf8(param, i, p);
+    if (c.momentum != 0.f) StateIO<F32>::store(buf, i, m);
   }
 }
 
@@ -315,6 +359,31 @@ extern "C" int rf_lora_adamw(void* param, const void* grad, void* exp_avg, void*
   else
     hipLaunchKernelGGL(adamw_kernel<false>, dim3(blocks), dim3(OPT_THREADS), 0, (hipStream_t)stream, (bf16_t*)param, (const bf16_t*)grad, exp_avg,
                        exp_avg_sq, n, c);
+  RF_LAUNCH_CHECK();
+  return RF_OK;
+}
+
+extern "C" int rf_lora_sgd(void* param, const void* grad, void* momentum_buffer, int64_t n, int32_t state_fp32, int32_t step, float lr,
+                           float momentum, float dampening, float weight_decay, int32_t nesterov, int32_t maximize, float grad_scale,
+                           void* stream) {
+  using namespace rf;
+  if (int rc = opt_check("rf_lora_sgd", param, grad, momentum_buffer, momentum_buffer, n)) return rc;
+  RF_REQUIRE(step >= 1 && momentum >= 0.f && weight_decay >= 0.f, RF_ERR_SHAPE, "rf_lora_sgd: step=%d momentum=%g weight_decay=%g", step, momentum,
+             weight_decay);
+  RF_REQUIRE(!nesterov || (momentum > 0.f && dampening == 0.f), RF_ERR_SHAPE,
+             "rf_lora_sgd: nesterov needs a momentum and zero dampening (momentum=%g dampening=%g)", momentum, dampening);   // as torch
+  SgdScalars c;
+  c.lr = lr, c.momentum = momentum, c.one_minus_dampening = (float)(1.0 - (double)dampening), c.weight_decay = weight_decay;
+  c.grad_scale = grad_scale, c.nesterov = nesterov ? 1 : 0, c.maximize = maximize ? 1 : 0, c.first = step == 1 ? 1 : 0;
+  const unsigned blocks = (unsigned)((n + OPT_BLOCK_ELEMS - 1) / OPT_BLOCK_ELEMS);
+  const double sb = momentum != 0.f ? (state_fp32 ? 4.0 : 2.0) : 0.0;
+  ProfScope prof(RF_KC_ROWOP, (double)n * (2.0 + 2.0 + 2.0 + 2.0 * sb), (hipStream_t)stream);
+  if (state_fp32)
+    hipLaunchKernelGGL(sgd_kernel<true>, dim3(blocks), dim3(OPT_THREADS), 0, (hipStream_t)stream, (bf16_t*)param, (const bf16_t*)grad, momentum_buffer,
+                       n, c);
+  else
+    hipLaunchKernelGGL(sgd_kernel<false>, dim3(blocks), dim3(OPT_THREADS), 0, (hipStream_t)stream, (bf16_t*)param, (const bf16_t*)grad, momentum_buffer,
+                       n, c);
   RF_LAUNCH_CHECK();
   return RF_OK;
 }

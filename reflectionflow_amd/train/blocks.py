@@ -219,6 +219,13 @@ def _acc(dst: Optional[torch.Tensor], g: torch.Tensor) -> torch.Tensor:
     return g if dst is None else dst + g
 
 
+def _attn_kw(st, attn_mode: int, cross_bias: float) -> dict:
+    """mode / n_main / cross_bias of ops.attention and K.attention_bwd for streams `st` whose last one holds the condition rows"""
+    if not attn_mode:
+        return {}
+    return dict(mode=int(attn_mode), n_main=st[-1].sl.start, cross_bias=float(cross_bias))
+
+
 # ------------------------------------------------------------------------------------------------------------------ DoubleStream
 def _double_streams(tw: TrainWeights, x_txt, x_img, x_cond, mod_txt, mod_img, mod_cond, latent_lora: bool) -> List[_Stream]:
     D = tw.D
@@ -233,11 +240,18 @@ def _double_streams(tw: TrainWeights, x_txt, x_img, x_cond, mod_txt, mod_img, mo
 
 
 def double_train_forward(tw: TrainWeights, x_txt, x_img, x_cond, mod_txt, mod_img, mod_cond, cos, sin, lora: dict,
-                         latent_lora: bool = False, keep: Optional[dict] = None, tc: Optional[dict] = None):
+                         latent_lora: bool = False, keep: Optional[dict] = None, tc: Optional[dict] = None,
+                         attn_mode: int = 0, cross_bias: float = 0.0, add_cond_attn: bool = False):
     """Training form of block.py:173-272 for ONE sample: x_* [rows, D] bf16, mod_* [6 D] bf16, lora = {"qkv": (A, Bs), "out": ...,
-    "ff2": ...} (entries may be (None, None)).  Returns [y_txt, y_img, y_cond?]; `keep` (a dict) receives the intermediates."""
+    "ff2": ...} (entries may be (None, None)).  Returns [y_txt, y_img, y_cond?]; `keep` (a dict) receives the intermediates.
+    attn_mode / cross_bias: rf_attention's mode over the (main <-> condition) pairs (block.py:106-122); add_cond_attn: the image rows
+    also receive the gated condition attention output (block.py:227-228)."""
     D, H, mlp = tw.D, tw.heads, tw.mlp
     st = _double_streams(tw, x_txt, x_img, x_cond, mod_txt, mod_img, mod_cond, latent_lora)
+    add_cond = bool(add_cond_attn) and x_cond is not None
+    if add_cond and x_cond.shape[0] != x_img.shape[0]:
+        raise ops.RFError(f"add_cond_attn needs S_cond == S_img (block.py:227-228), got {x_cond.shape[0]} and {x_img.shape[0]}")
+    akw = _attn_kw(st, attn_mode, cross_bias) if x_cond is not None else {}     # no condition rows, no cross pair: the plain launch
     S, dev = sum(s.rows for s in st), x_img.device
     new = lambda *shape: torch.empty(*shape, dtype=BF, device=dev)   # noqa: E731
     XN, RAW = new(S, D), new(S, 3 * D)
@@ -248,12 +262,15 @@ def double_train_forward(tw: TrainWeights, x_txt, x_img, x_cond, mod_txt, mod_im
     a = K.qkv_train_fwd(RAW, H, st[0].rows, norms, cos, sin, backward_operands=keep is not None)
     # (recompute inside the backward: the forward kernel also emits the row statistics its backward needs)
     LSE = torch.empty(H, a.s_pad, dtype=torch.float32, device=dev) if keep is not None else None
-    ATT = ops.attention(a.q, a.k, a.vt, S, q_prescaled=True, score_bound=0.0, lse=LSE)
+    ATT = ops.attention(a.q, a.k, a.vt, S, q_prescaled=True, score_bound=0.0, lse=LSE, **akw)
     AOUT = new(S, D)
     _grouped(st, ATT, [(tw,) + s.out for s in st], D, AOUT, lora.get("out"), keep, "out", tc)
     X1, XN2 = new(S, D), new(S, D)
-    for s in st:
-        K.gate_residual(AOUT[s.sl], s.mod[2], s.x, out=X1[s.sl])
+    for i, s in enumerate(st):
+        if add_cond and i == 1:      # hidden_states = hidden_states + gate_msa o attn + cond_gate_msa o cond_attn
+            K.gate_residual(AOUT[st[2].sl], st[2].mod[2], K.gate_residual(AOUT[s.sl], s.mod[2], s.x), out=X1[s.sl])
+        else:
+            K.gate_residual(AOUT[s.sl], s.mod[2], s.x, out=X1[s.sl])
         ops.layernorm_modulate(X1[s.sl], s.mod[4], s.mod[3], out=XN2[s.sl])
     Z1 = new(S, mlp)
     _grouped(st, XN2, [(tw,) + s.ff1 for s in st], mlp, Z1)
@@ -264,7 +281,8 @@ def double_train_forward(tw: TrainWeights, x_txt, x_img, x_cond, mod_txt, mod_im
     for s in st:
         K.gate_residual(FF[s.sl], s.mod[5], X1[s.sl], out=Y[s.sl])
     if keep is not None:
-        keep.update(st=st, XN=XN, RAW=RAW, a=a, ATT=ATT, LSE=LSE, AOUT=AOUT, X1=X1, XN2=XN2, Z1=Z1, HH=HH, FF=FF, norms=norms)
+        keep.update(st=st, XN=XN, RAW=RAW, a=a, ATT=ATT, LSE=LSE, AOUT=AOUT, X1=X1, XN2=XN2, Z1=Z1, HH=HH, FF=FF, norms=norms,
+                    attn_kw=akw, add_cond=add_cond)
     return [Y[s.sl] for s in st]
 
 
@@ -312,11 +330,14 @@ def double_train_backward(tw: TrainWeights, kp: dict, dys: Sequence[torch.Tensor
     # x1 = x + gate_msa o a_out
     DAO = new(S, D)
     for i, s in enumerate(st):
-        _, dmod[i][2] = K.gate_bwd(DX1[s.sl], kp["AOUT"][s.sl], s.mod[2], out=DAO[s.sl], need_dmod=nd[i])
+        dx1 = DX1[s.sl]
+        if kp.get("add_cond") and i == 2:      # the gated condition attention output also went into the image rows (block.py:227-228)
+            dx1 = dx1 + DX1[st[1].sl]
+        _, dmod[i][2] = K.gate_bwd(dx1, kp["AOUT"][s.sl], s.mod[2], out=DAO[s.sl], need_dmod=nd[i])
     dTs, A = lora_of("out", kp["ATT"], DAO)
     DATT = new(S, D)
     _dx_grouped(st, DAO, [(tw, s.out[0], None) for s in st], D, DATT, dTs, A)
-    dq, dk, dv = K.attention_bwd(kp["a"], kp["ATT"], DATT, lse=kp.get("LSE"))
+    dq, dk, dv = K.attention_bwd(kp["a"], kp["ATT"], DATT, lse=kp.get("LSE"), **kp.get("attn_kw", {}))
     DRAW = new(S, 3 * D)
     K.qkv_train_bwd(kp["RAW"], H, st[0].rows, kp["norms"], cos, sin, dq, dk, dv, DRAW)
     dTs, A = lora_of("qkv", kp["XN"], DRAW)
@@ -337,10 +358,20 @@ class BlockOpts(NamedTuple):
     backward, so the gradients are bit-identical, with one forward less per block and step."""
     latent_lora: bool = False
     recompute: bool = True
+    attn_mode: int = 0          # rf_attention's mode over the (main <-> condition) pairs, from engine.make_dims (block.py:106-122)
+    cross_bias: float = 0.0     # mode 1: log(c_factor)
+    add_cond_attn: bool = False  # DoubleStream blocks only (block.py:227-228)
 
 
 def _opts(o) -> BlockOpts:
     return o if isinstance(o, BlockOpts) else BlockOpts(bool(o), True)
+
+
+def _fwd_kw(o: BlockOpts, double: bool) -> dict:
+    kw = dict(attn_mode=o.attn_mode, cross_bias=o.cross_bias)
+    if double:
+        kw["add_cond_attn"] = o.add_cond_attn
+    return kw
 
 
 class DoubleBlockFn(torch.autograd.Function):
@@ -349,11 +380,14 @@ class DoubleBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tw, opts, x_txt, x_img, x_cond, mod_txt, mod_img, mod_cond, cos, sin, *lo):
-        latent_lora, recompute = _opts(opts)
+        opts = _opts(opts)
+        latent_lora, recompute = opts.latent_lora, opts.recompute
         lora = {"qkv": (lo[0], lo[1]), "out": (lo[2], lo[3]), "ff2": (lo[4], lo[5])}
         ctx.tc = {}
         ctx.kp = None if recompute else {}
-        ys = double_train_forward(tw, x_txt, x_img, x_cond, mod_txt, mod_img, mod_cond, cos, sin, lora, latent_lora, keep=ctx.kp, tc=ctx.tc)
+        ctx.fwd_kw = _fwd_kw(opts, True)
+        ys = double_train_forward(tw, x_txt, x_img, x_cond, mod_txt, mod_img, mod_cond, cos, sin, lora, latent_lora, keep=ctx.kp, tc=ctx.tc,
+                                  **ctx.fwd_kw)
         ctx.tw, ctx.latent_lora, ctx.has_cond = tw, latent_lora, x_cond is not None
         ctx.save_for_backward(x_txt, x_img, x_cond, mod_txt, mod_img, mod_cond, cos, sin, *lo)
         return (ys[0], ys[1], ys[2] if x_cond is not None else None)
@@ -366,7 +400,8 @@ class DoubleBlockFn(torch.autograd.Function):
         ctx.kp = None                                            # (the intermediates die with this call)
         if kp is None:
             kp = {}
-            double_train_forward(ctx.tw, x_txt, x_img, x_cond, mod_txt, mod_img, mod_cond, cos, sin, lora, ctx.latent_lora, keep=kp, tc=ctx.tc)   # recompute
+            double_train_forward(ctx.tw, x_txt, x_img, x_cond, mod_txt, mod_img, mod_cond, cos, sin, lora, ctx.latent_lora, keep=kp, tc=ctx.tc,
+                                 **ctx.fwd_kw)   # recompute
         zeros = lambda x: torch.zeros_like(x)   # noqa: E731
         dys = [dy_txt if dy_txt is not None else zeros(x_txt), dy_img if dy_img is not None else zeros(x_img)]
         if ctx.has_cond:
@@ -380,7 +415,7 @@ class DoubleBlockFn(torch.autograd.Function):
 
 # ------------------------------------------------------------------------------------------------------------------ SingleStream
 def single_train_forward(tw: TrainWeights, x_main, x_cond, mod_main, mod_cond, cos, sin, lora: dict, latent_lora: bool = False,
-                         keep: Optional[dict] = None, tc: Optional[dict] = None):
+                         keep: Optional[dict] = None, tc: Optional[dict] = None, attn_mode: int = 0, cross_bias: float = 0.0):
     """Training form of block.py:275-333 for ONE sample: x_main = [text; image] rows, mod_* [3 D] = (shift, scale, gate);
     lora = {"qkv_mlp": (A [r, D], Bs [3 D + mlp, r]), "out": (A [r, D + mlp], Bs [D, r])}."""
     D, H, mlp = tw.D, tw.heads, tw.mlp
@@ -390,6 +425,7 @@ def single_train_forward(tw: TrainWeights, x_main, x_cond, mod_main, mod_cond, c
     if x_cond is not None:
         st.append(_Stream(x_cond, ch(mod_cond), x_main.shape[0], True, **names))
     S, dev = sum(s.rows for s in st), x_main.device
+    akw = _attn_kw(st, attn_mode, cross_bias) if x_cond is not None else {}     # no condition rows, no cross pair: the plain launch
     new = lambda *shape: torch.empty(*shape, dtype=BF, device=dev)   # noqa: E731
     XN, Z = new(S, D), new(S, 3 * D + mlp)
     for s in st:
@@ -399,7 +435,7 @@ def single_train_forward(tw: TrainWeights, x_main, x_cond, mod_main, mod_cond, c
     a = K.qkv_train_fwd(Z, H, 0, norms, cos, sin, backward_operands=keep is not None)
     # (recompute inside the backward: the forward kernel also emits the row statistics its backward needs)
     LSE = torch.empty(H, a.s_pad, dtype=torch.float32, device=dev) if keep is not None else None
-    ATT = ops.attention(a.q, a.k, a.vt, S, q_prescaled=True, score_bound=0.0, lse=LSE)
+    ATT = ops.attention(a.q, a.k, a.vt, S, q_prescaled=True, score_bound=0.0, lse=LSE, **akw)
     HM = K.gelu(Z[:, 3 * D:])
     FF = new(S, D)
     A_o, B_o = lora.get("out", (None, None))
@@ -423,7 +459,7 @@ def single_train_forward(tw: TrainWeights, x_main, x_cond, mod_main, mod_cond, c
     for s in st:
         K.gate_residual(FF[s.sl], s.mod[2], s.x, out=Y[s.sl])
     if keep is not None:
-        keep.update(st=st, XN=XN, Z=Z, a=a, ATT=ATT, LSE=LSE, HM=HM, FF=FF, norms=norms)
+        keep.update(st=st, XN=XN, Z=Z, a=a, ATT=ATT, LSE=LSE, HM=HM, FF=FF, norms=norms, attn_kw=akw)
     return [Y[s.sl] for s in st]
 
 
@@ -453,7 +489,7 @@ def single_train_backward(tw: TrainWeights, kp: dict, dys: Sequence[torch.Tensor
     _dx_grouped(st, DF, [(tw, "w_out", None) for _ in st], D + mlp, DCAT, dTs, A_o)
     DZ = new(S, 3 * D + mlp)
     K.gelu_bwd(kp["Z"][:, 3 * D:], DCAT[:, D:], out=DZ[:, 3 * D:])
-    dq, dk, dv = K.attention_bwd(kp["a"], kp["ATT"], DCAT[:, :D], lse=kp.get("LSE"))
+    dq, dk, dv = K.attention_bwd(kp["a"], kp["ATT"], DCAT[:, :D], lse=kp.get("LSE"), **kp.get("attn_kw", {}))
     K.qkv_train_bwd(kp["Z"], H, 0, kp["norms"], cos, sin, dq, dk, dv, DZ)
     A_q, B_q = lora.get("qkv_mlp", (None, None))
     dTs = {}
@@ -478,11 +514,13 @@ class SingleBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tw, opts, x_main, x_cond, mod_main, mod_cond, cos, sin, *lo):
-        latent_lora, recompute = _opts(opts)
+        opts = _opts(opts)
+        latent_lora, recompute = opts.latent_lora, opts.recompute
         lora = {"qkv_mlp": (lo[0], lo[1]), "out": (lo[2], lo[3])}
         ctx.tc = {}
         ctx.kp = None if recompute else {}
-        ys = single_train_forward(tw, x_main, x_cond, mod_main, mod_cond, cos, sin, lora, latent_lora, keep=ctx.kp, tc=ctx.tc)
+        ctx.fwd_kw = _fwd_kw(opts, False)
+        ys = single_train_forward(tw, x_main, x_cond, mod_main, mod_cond, cos, sin, lora, latent_lora, keep=ctx.kp, tc=ctx.tc, **ctx.fwd_kw)
         ctx.tw, ctx.latent_lora, ctx.has_cond = tw, latent_lora, x_cond is not None
         ctx.save_for_backward(x_main, x_cond, mod_main, mod_cond, cos, sin, *lo)
         return (ys[0], ys[1] if x_cond is not None else None)
@@ -495,7 +533,8 @@ class SingleBlockFn(torch.autograd.Function):
         ctx.kp = None
         if kp is None:
             kp = {}
-            single_train_forward(ctx.tw, x_main, x_cond, mod_main, mod_cond, cos, sin, lora, ctx.latent_lora, keep=kp, tc=ctx.tc)    # recompute
+            single_train_forward(ctx.tw, x_main, x_cond, mod_main, mod_cond, cos, sin, lora, ctx.latent_lora, keep=kp, tc=ctx.tc,
+                                 **ctx.fwd_kw)    # recompute
         dys = [dy_main if dy_main is not None else torch.zeros_like(x_main)]
         if ctx.has_cond:
             dys.append(dy_cond if dy_cond is not None else torch.zeros_like(x_cond))

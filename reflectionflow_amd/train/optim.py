@@ -6,7 +6,7 @@ second one (autograd accumulates into an existing .grad in place, so the backwar
 
   * the data-parallel reduction is `all_reduce(bucket.grad)` on the buffer as it lies -- no pack, no unpack, no per-tensor averaging:
     the 1 / world_size rides into the update kernel as `grad_scale`  (round 4: zeros + 354 slice copies in, 354 copies out);
-  * zero_grad is one memset, the update is one launch (AdamW) or three (Prodigy) of csrc/optim.hip instead of a multi-tensor foreach;
+  * zero_grad is one memset, the update is one launch (AdamW, SGD) or three (Prodigy) of csrc/optim.hip instead of a multi-tensor foreach;
   * Prodigy's distance estimate d stays on the device: nothing crosses to the host inside a step (prodigyopt reads one .item() per
     parameter tensor and step, i.e. 354 host syncs).
 
@@ -79,8 +79,8 @@ class _FlatOptimizer:
             raise RFError("optimizer state must be bf16 (what torch / prodigyopt keep for bf16 parameters) or fp32")
         self.state_fp32 = state_dtype == torch.float32
         n, dev = self.bucket.numel, self.bucket.param.device
-        self.exp_avg = torch.zeros(n, dtype=state_dtype, device=dev)
-        self.exp_avg_sq = torch.zeros(n, dtype=state_dtype, device=dev)
+        for name in self._MOMENTS:                                # flat state buffers of the bucket's size
+            setattr(self, name, torch.zeros(n, dtype=state_dtype, device=dev))
         self.grad_scale = 1.0                                     # set to 1 / world_size behind bucket.all_reduce()
         self.lib = L.load()
         self._clip_ws = self._clip_out = None
@@ -106,6 +106,7 @@ class _FlatOptimizer:
                                                 self._clip_ws.numel() * 4, self._clip_out.data_ptr(), stream_ptr()), "rf_lora_clip_grad_norm")
         return self._clip_out
 
+    _MOMENTS: tuple = ("exp_avg", "exp_avg_sq")
     _STATE_TENSORS: tuple = ()
 
     def load_state_dict(self, sd: Dict) -> None:
@@ -143,6 +144,41 @@ class LoraAdamW(_FlatOptimizer):
 
     def state_dict(self) -> Dict:
         return dict(step=self.step_count, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, **self.defaults)
+
+    def load_state_dict(self, sd: Dict) -> None:
+        super().load_state_dict(sd)
+        self.step_count = int(sd["step"])
+
+
+class LoraSGD(_FlatOptimizer):
+    """torch.optim.SGD's update (sgd.py::_single_tensor_sgd: momentum, dampening, nesterov, weight decay, maximize) as ONE launch of
+    rf_lora_sgd, rounding to bf16 where torch's tensor ops on bf16 parameters round.  The momentum buffer is torch's
+    `momentum_buffer` (a copy of the first step's gradient, as torch initialises it); with momentum = 0 it is never touched."""
+
+    _MOMENTS = ("momentum_buffer",)
+
+    def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0, nesterov: bool = False,
+                 maximize: bool = False, state_dtype: torch.dtype = BF):
+        if lr < 0 or momentum < 0 or weight_decay < 0:
+            raise RFError(f"SGD: lr, momentum and weight_decay must be >= 0 (got {lr}, {momentum}, {weight_decay})")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise RFError("SGD: nesterov momentum requires a momentum and zero dampening")          # torch's own rule
+        super().__init__(params, state_dtype)
+        self.defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, maximize=maximize)
+        self.step_count = 0
+
+    @torch.no_grad()
+    def step(self) -> None:
+        d, b = self.defaults, self.bucket
+        self.step_count += 1
+        L.check(self.lib.rf_lora_sgd(b.param.data_ptr(), b.grad.data_ptr(), self.momentum_buffer.data_ptr(), b.numel, int(self.state_fp32),
+                                     self.step_count, d["lr"], d["momentum"], d["dampening"], d["weight_decay"], int(d["nesterov"]),
+                                     int(d["maximize"]), self.grad_scale, stream_ptr()), "rf_lora_sgd")
+
+    _STATE_TENSORS = ("momentum_buffer",)
+
+    def state_dict(self) -> Dict:
+        return dict(step=self.step_count, momentum_buffer=self.momentum_buffer, **self.defaults)
 
     def load_state_dict(self, sd: Dict) -> None:
         super().load_state_dict(sd)
@@ -197,5 +233,5 @@ def build_optimizer(params, optimizer_config: Dict, state_dtype: torch.dtype = B
     if kind == "Prodigy":
         return LoraProdigy(params, state_dtype=state_dtype, **kw)
     if kind == "SGD":
-        raise RFError("optimizer type SGD: use torch.optim.SGD on lora_parameters() (no HIP kernel; the shipped config trains with Prodigy)")
+        return LoraSGD(params, state_dtype=state_dtype, **kw)
     raise NotImplementedError(kind)                                # as the reference (model.py:116-117)

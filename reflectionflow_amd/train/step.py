@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from .. import engine as E
 from .. import ops
 from ..flux.modules import LoraLinear
+from ..flux.transformer import _attn_c_factor
 from .blocks import BlockOpts, DoubleBlockFn, SingleBlockFn, double_weights, fused_lora, single_weights
 
 BF = torch.bfloat16
@@ -110,8 +111,6 @@ class FluxTrainer:
             raise ops.RFError(f"gradient_clip_val must be >= 0 or None, got {gradient_clip_val!r}")
         self.gradient_clip_val = gradient_clip_val or None
         self.kept_blocks = 0                                # blocks of the last forward that kept their intermediates (telemetry)
-        if self.cfg.get("add_cond_attn", False) or not self.cfg.get("union_cond_attn", True):
-            raise ops.RFError("the training path covers the shipped training config (union_cond_attn: true, add_cond_attn: false)")
         E.check_lora_placement(transformer)
         if getattr(transformer, "_rf_merged_lora", False):
             raise ops.RFError("training needs the LoRA factors as factors: call pipe.enable_merged_lora(False) first")
@@ -132,7 +131,7 @@ class FluxTrainer:
 
     def configure_optimizers(self, optimizer_config: Optional[dict] = None, state_dtype: torch.dtype = BF):
         """train/model.py:94-117 (`configure_optimizers`): the optimizer over the LoRA factors, built from the reference's
-        `optimizer_config` ({"type": "Prodigy" | "AdamW", "params": {...}}; default: the shipped config.yaml:55-61).  The factors move
+        `optimizer_config` ({"type": "Prodigy" | "AdamW" | "SGD", "params": {...}}; default: the shipped config.yaml:55-61).  The factors move
         into ONE flat bucket (train/optim.py: gradients accumulate straight into it, the data-parallel all-reduce and the update run on
         it as it lies), so the engine's packed pointers are re-made."""
         from .optim import build_optimizer
@@ -368,6 +367,13 @@ class FluxTrainer:
                 - torch.cuda.memory_allocated(hidden_states.device)
             budget = int(0.85 * free) - (16 << 30)
         self.kept_blocks = 0
+        # attention mode of every block: the ONE place that encodes block.py:106-122 (c_factor on the attention modules overrides the
+        # boolean mask; no condition rows, no cross pair).  add_cond_attn concerns the DoubleStream blocks only (block.py:227-228).
+        Sc = condition_latents.shape[1] if use_cond else 0
+        dims = eng.dims(encoder_hidden_states.shape[1], hidden_states.shape[1], Sc, self.cfg, _attn_c_factor(tr))      # engine.make_dims
+        attn_mode, cross_bias, add_cond = int(dims.attn_mode), float(dims.cross_bias), bool(dims.add_cond_attn) and use_cond
+        if add_cond and Sc != hidden_states.shape[1]:
+            raise ops.RFError(f"add_cond_attn needs S_cond == S_img (block.py:227-228), got {Sc} and {hidden_states.shape[1]}")
 
         def opts(cost):
             nonlocal budget
@@ -379,7 +385,7 @@ class FluxTrainer:
             if keep:
                 budget -= cost
                 self.kept_blocks += 1
-            return BlockOpts(self.latent_lora, not keep)
+            return BlockOpts(self.latent_lora, not keep, attn_mode, cross_bias, add_cond)
         for b in range(hidden_states.shape[0]):
             m_img, m_txt, m_sgl, m_out = self._mods(temb[b:b + 1], self.latent_lora)
             if use_cond:
