@@ -10,11 +10,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.attn_fwd_cases import BF, assert_close, make_qkv, rnd, vt_unpermute   # noqa: F401  (shared with the other GPU suites)
 from tests.pins import pins
 
 pytestmark = pytest.mark.gpu
-
-BF = torch.bfloat16
 
 
 @pytest.fixture(scope="module")
@@ -24,29 +23,6 @@ def dev():
     from reflectionflow_amd import _lib
     _lib.load()  # fail loudly if the HIP library is missing
     return torch.device("cuda:0")
-
-
-def rnd(*shape, dev, scale=1.0, seed=None):
-    g = torch.Generator(device="cpu")
-    g.manual_seed(seed if seed is not None else (hash(shape) % 100000))
-    return (torch.randn(*shape, generator=g) * scale).to(dev).to(BF)
-
-
-def assert_close(got, ref, what, rtol=1.2e-2, atol=None):
-    got, ref = got.float(), ref.float()
-    assert got.shape == ref.shape, f"{what}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
-    assert torch.isfinite(got).all(), f"{what}: non-finite output"
-    if atol is None:
-        atol = 1.2e-2 * float(ref.abs().mean()) + 1e-6
-    err = (got - ref).abs()
-    bad = err > atol + rtol * ref.abs()
-    rel_l2 = float((got - ref).norm() / (ref.norm() + 1e-12))
-    if bad.any():
-        idx = torch.nonzero(bad)[:8].tolist()
-        raise AssertionError(f"{what}: {int(bad.sum())}/{bad.numel()} elements off, max err {float(err.max()):.4g}, "
-                             f"rel-L2 {rel_l2:.3e}, first bad idx {idx}, got {got[bad][:4].tolist()} ref {ref[bad][:4].tolist()}")
-    assert rel_l2 < 4e-3, f"{what}: rel-L2 {rel_l2:.3e}"
-    return rel_l2
 
 
 # ------------------------------------------------------------------------------------- GEMM
@@ -124,15 +100,6 @@ def test_gemm_epilogues_and_segments(dev, tile):
             assert_close(outs[i], ref, f"group {i}")
     finally:
         pins.reset()
-
-
-def vt_unpermute(vt, S):
-    """[H, S_pad/64, 128, 64] key-permuted V^T tiles -> [H, S, 128]."""
-    H, nt = vt.shape[0], vt.shape[1]
-    kv = torch.arange(64, device=vt.device)
-    pos = (kv & 51) | ((kv & 4) << 1) | ((kv & 8) >> 1)
-    v = vt[:, :, :, pos]                      # [H, nt, 128, 64(kv)]
-    return v.permute(0, 1, 3, 2).reshape(H, nt * 64, 128)[:, :S]
 
 
 @pytest.mark.parametrize("tile", [128, 256, 257])
@@ -234,23 +201,6 @@ def test_elementwise(dev):
 
 
 # ------------------------------------------------------------------------------------- attention
-def make_qkv(H, S, dev, seed=0, qscale=1.0):
-    from reflectionflow_amd import ops
-    q, k, vt, s_pad = ops.alloc_attn_operands(H, S, dev)
-    qf = rnd(H, S, 128, dev=dev, seed=seed + 1, scale=qscale)
-    kf = rnd(H, S, 128, dev=dev, seed=seed + 2)
-    vf = rnd(H, S, 128, dev=dev, seed=seed + 3)
-    q[:, :S], k[:, :S] = qf, kf
-    kv = torch.arange(s_pad, device=dev)
-    pos = (kv & ~63) | (kv & 51) | ((kv & 4) << 1) | ((kv & 8) >> 1)
-    vpad = torch.zeros(H, s_pad, 128, device=dev, dtype=BF)
-    vpad[:, :S] = vf
-    vperm = torch.empty_like(vpad)
-    vperm[:, pos] = vpad                               # permuted position <- key
-    vt.copy_(vperm.reshape(H, s_pad // 64, 64, 128).permute(0, 1, 3, 2))
-    return q, k, vt, qf, kf, vf
-
-
 def sdpa_ref(qf, kf, vf, mask=None):
     o = F.scaled_dot_product_attention(qf.float()[None], kf.float()[None], vf.float()[None], attn_mask=mask)
     return o[0].permute(1, 0, 2).reshape(qf.shape[1], -1)

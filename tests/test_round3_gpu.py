@@ -17,7 +17,7 @@ import os
 import pytest
 import torch
 
-from tests.test_kernels_gpu import BF, assert_close, make_qkv
+from tests.attn_fwd_cases import BF, assert_close, prescaled, softmax_ref64   # noqa: F401
 from tests.test_model_gpu import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -30,23 +30,6 @@ def dev():
     from reflectionflow_amd import _lib
     _lib.load()
     return torch.device("cuda:0")
-
-
-def softmax_ref64(qp, kf, vf):
-    """fp64 softmax(q k^T) v in the exp2 domain (q already carries scale * log2 e): [H,S,128] x3 -> [S, H*128] fp32."""
-    s = torch.einsum("hqd,hkd->hqk", qp.double(), kf.double())
-    s = s - s.amax(dim=-1, keepdim=True)
-    p = torch.exp2(s)
-    o = torch.einsum("hqk,hkd->hqd", p / p.sum(-1, keepdim=True), vf.double())
-    return o.permute(1, 0, 2).reshape(qp.shape[1], -1).float()
-
-
-def prescaled(H, S, dev, seed, qscale=1.0):
-    from reflectionflow_amd import ops
-    q, k, vt, qf, kf, vf = make_qkv(H, S, dev, seed=seed, qscale=qscale)
-    qp = (qf.float() * ops.QK_PRESCALE).to(BF)
-    q[:, :S] = qp
-    return q, k, vt, qp, kf, vf
 
 
 @pytest.mark.parametrize("S,H", [(256, 3), (1024, 8), (2048, 8), (4608, 8), (5632, 8)])

@@ -181,18 +181,19 @@ def test_attention_bwd_vs_fp32_autograd(dev, H, S):
     # may pick must write log2-sum-exp2 of the scaled score rows, and the gradients must meet the same bound
     s2 = qf.detach().double() @ kf.detach().double().transpose(1, 2)
     lse_ref = torch.logsumexp(s2 * LN2, -1) / LN2                                  # log2 sum_k 2^s2
-    from reflectionflow_amd import _lib as L
     # (|s2| <= 128 * 0.128 here: the bounded kernels may run with score_bound = 100)
-    kernels = [(None, 0.0), (L.RF_ATTN_ONLINE128, 0.0), (L.RF_ATTN_ONLINE256, 0.0), (L.RF_ATTN_BOUNDED32, 100.0), (L.RF_ATTN_BOUNDED16, 100.0),
-               (L.RF_ATTN_BOUNDED16_SPLIT, 100.0), (L.RF_ATTN_LAGGED16, 0.0), (L.RF_ATTN_LAGGED16_SPLIT, 0.0), (L.RF_ATTN_BOUNDED16_MIX, 100.0),
-               (L.RF_ATTN_LAGGED16_MIX, 0.0)]
+    # every form must run exactly where its precondition holds (tests/attn_fwd_cases.form_runs) and fail loudly elsewhere
+    from tests import attn_fwd_cases as AF
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    kernels = [(None, 0.0, True)] + [(f.kernel, 100.0 if f.bounded else 0.0, AF.form_runs(f, H, S, cus)) for f in AF.FORMS + AF.SPLIT_FORMS]
     ran = 0
-    for kern, bound in kernels:
+    for kern, bound, runs in kernels:
         lse = torch.full((H, a.s_pad), float("nan"), dtype=torch.float32, device=dev)
-        try:
-            out2 = ops.attention(a.q, a.k, a.vt, S, q_prescaled=True, lse=lse, kernel=kern, score_bound=bound)
-        except ops.RFError:
-            continue                                                                # this kernel cannot run this shape
+        if not runs:
+            with pytest.raises(ops.RFError):                                        # this kernel cannot run this shape
+                ops.attention(a.q, a.k, a.vt, S, q_prescaled=True, lse=lse, kernel=kern, score_bound=bound)
+            continue
+        out2 = ops.attention(a.q, a.k, a.vt, S, q_prescaled=True, lse=lse, kernel=kern, score_bound=bound)
         ran += 1
         assert torch.equal(out2, out) or rel_l2(out2, out) < 2e-2
         err = float((lse[:, :S].double() - lse_ref).abs().max())
