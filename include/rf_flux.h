@@ -466,7 +466,11 @@ typedef struct rf_vae_weights {                 /* ONE direction: the Decoder or
  * an earlier launch of the same call.  That includes the up to fold - 1 pixels behind an image that the last GEMM row of a folded
  * convolution multiplies against zero weight columns (0 x NaN is NaN): the kernels that produce a convolution's input write zeros
  * over the 64 pixels behind it, and the size returned here has the room.  The one buffer the library cannot prepare is the
- * caller's input -- INPUT SLACK below. */
+ * caller's input -- INPUT SLACK below.
+ * GEOMETRY: any h, w >= 1 (encode: sides that the downsamplers halve evenly).  The mid-block attention (has_attn, C == 512) runs over
+ * S = the bottleneck's H W tokens, any S >= 1: its q | k rows and V^T row pitch are padded to S_pad = S rounded up to a multiple of 64,
+ * the launches write rows / columns 0 .. S - 1 only, and the kernel masks the key tail (scores by select, V^T operand zeroed), so the pad
+ * holds whatever the workspace held -- the rule above.  S % 64 == 0: S_pad == S, the same bytes and the same kernel as before. */
 int64_t rf_vae_workspace_bytes(const rf_vae_weights* w, int32_t encode, int32_t h, int32_t w_in);
 /* INPUT SLACK (both entry points): conv_in runs as a GEMM whose 64-element K-tiles reach past the last pixel's channels against zero
  * weight columns, so the input buffer must be followed by >= 64 * max(conv_in.cin, 64) * 2 readable bytes holding FINITE values

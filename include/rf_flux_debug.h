@@ -91,12 +91,17 @@ int rf_debug_text_attention(int32_t head_dim, int32_t qi, const void* q, int64_t
  *   ATTN_CORE   vae_attn_kernel alone: in = qk [S][1024] (q | k), residual = vt [512][S], out [S][512]; S = H*W, C = 512
  *   ATTN_BLOCK  the mid-block attention in place: out = padded [(H+2)(W+2)][512], x += to_out(attn(group_norm(x))); halo neither read
  *               nor written; `attn`, `groups`; `in` unused
+ *   ATTN_CORE and ATTN_BLOCK take S = H*W % 64 == 0 only (the kernel without a key tail); the two ops below take ANY S >= 1 and run that
+ *   same kernel when S % 64 == 0, its ragged instantiation (last key tile masked) otherwise.  S_pad = S rounded up to a multiple of 64.
+ *   ATTN_CORE_RAGGED   in = qk [S_pad][1024] (q | k), residual = vt [512][S_pad] (row pitch S_pad), out [S][512]; rows S .. of qk and
+ *               columns S .. of a vt row may hold anything (NaN included): no result depends on them; neither input is written
+ *   ATTN_BLOCK_RAGGED  the contract of ATTN_BLOCK
  * ws == NULL (or ws->base == NULL): returns the workspace bytes the op needs (> 0) instead of running; the workspace's contents on
  * entry do not matter.  Otherwise returns RF_OK or an RF_ERR_* status. */
 #define RF_VAE_TAIL_PIXELS 64
 typedef enum rf_vae_op {
   RF_VAE_OP_GROUP_NORM = 0, RF_VAE_OP_CONV3X3 = 1, RF_VAE_OP_UPSAMPLE2X = 2, RF_VAE_OP_DOWNSAMPLE = 3, RF_VAE_OP_ATTN_CORE = 4,
-  RF_VAE_OP_ATTN_BLOCK = 5
+  RF_VAE_OP_ATTN_BLOCK = 5, RF_VAE_OP_ATTN_CORE_RAGGED = 6, RF_VAE_OP_ATTN_BLOCK_RAGGED = 7
 } rf_vae_op;
 typedef struct rf_vae_op_desc {
   int32_t op;                       /* rf_vae_op */
@@ -105,7 +110,7 @@ typedef struct rf_vae_op_desc {
   int32_t _pad;
   const rf_vae_norm* norm;          /* GROUP_NORM */
   const rf_vae_conv* conv;          /* CONV3X3, DOWNSAMPLE */
-  const rf_vae_attn* attn;          /* ATTN_BLOCK */
+  const rf_vae_attn* attn;          /* ATTN_BLOCK, ATTN_BLOCK_RAGGED */
   const void* in; void* out; const void* residual;
   const rf_workspace* ws;
 } rf_vae_op_desc;

@@ -151,6 +151,7 @@ class rf_vae_op_desc(C.Structure):
 
 
 RF_VAE_OP_GROUP_NORM, RF_VAE_OP_CONV3X3, RF_VAE_OP_UPSAMPLE2X, RF_VAE_OP_DOWNSAMPLE, RF_VAE_OP_ATTN_CORE, RF_VAE_OP_ATTN_BLOCK = range(6)
+RF_VAE_OP_ATTN_CORE_RAGGED, RF_VAE_OP_ATTN_BLOCK_RAGGED = 6, 7      # any H * W >= 1 tokens (rf_flux_debug.h)
 RF_VAE_TAIL_PIXELS = 64
 
 

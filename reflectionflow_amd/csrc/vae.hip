@@ -254,6 +254,13 @@ __global__ __launch_bounds__(256) void fill_bf16_kernel(bf16_t* __restrict__ p, 
 // in lane group g; the PV product's B operand (P^T) of lane group g is {T0 keys 4g.., T1 keys 16 + 4g..} -- so its A operand
 // (V^T fragment) reads exactly those two 4-key runs of a row (2 x ds_read_b64).  Fragment reads run one group of four ahead of
 // their MFMAs through a register double buffer fenced by sched_barrier(0) (left alone, hipcc sinks every ds_read to its use).
+// RAGGED = false is the kernel for S % 64 == 0 (whole key tiles, V^T row pitch S; ldv is not read).  RAGGED = true takes any S >= 1:
+// qk has S_pad = round_up(S, 64) rows, vt a row pitch of ldv = S_pad elements, the grid is S_pad / 64, and the key loop runs
+// cdiv(S, 32) tiles -- the last one holds 0..31 pad keys, never 32, so every query's running max is finite after tile 0.  Pad rows of qk
+// and pad columns of vt hold WHATEVER (NaN included) and nothing depends on them: in the last tile (a wave-uniform branch; the tiles
+// before it run the schedule above) a score of key >= S becomes the -1e30 sentinel by SELECT after scaling (a NaN score only sits in
+// its own key's row of S^T), its probability is forced to 0, and the V^T fragment elements of those keys are forced to 0 (0 x NaN in
+// the PV MFMA).  The tile DMA reads key rows < 32 cdiv(S, 32) <= S_pad and the same columns of a vt row: inside both operands.
 constexpr int VA_C = 512;
 constexpr int VA_KT = 32;                       // keys per tile
 constexpr int VA_KBYTES = VA_KT * VA_C * 2;     // 32 KiB
@@ -261,8 +268,9 @@ constexpr int VA_VPITCH = 64;
 constexpr int VA_VBYTES = VA_C * VA_VPITCH;     // 32 KiB
 constexpr int VA_LDS = 2 * (VA_KBYTES + VA_VBYTES);
 
+template <bool RAGGED>
 __global__ __launch_bounds__(512) void vae_attn_kernel(const bf16_t* __restrict__ qk, const bf16_t* __restrict__ vt, bf16_t* __restrict__ out,
-                                                       int S, float scale_log2e) {
+                                                       int S, float scale_log2e, int ldv) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -294,7 +302,7 @@ __global__ __launch_bounds__(512) void vae_attn_kernel(const bf16_t* __restrict_
     const int row = 8 * i + w;
     k_src[i] = (uint32_t)(row * (int)ldqk * 2 + ((lane ^ (row & 15)) << 4));
     const int d = 16 * (8 * i + w) + (lane >> 2);
-    v_src[i] = (uint32_t)(((int64_t)d * S) * 2 + (((lane & 3) ^ ((d >> 2) & 3)) << 4));
+    v_src[i] = (uint32_t)(((int64_t)d * (RAGGED ? ldv : S)) * 2 + (((lane & 3) ^ ((d >> 2) & 3)) << 4));
   }
   auto dma_tile = [&](const int t, const int buf) {
     char* kb = smem + buf * (VA_KBYTES + VA_VBYTES);
@@ -306,7 +314,9 @@ __global__ __launch_bounds__(512) void vae_attn_kernel(const bf16_t* __restrict_
     }
   };
 
-  const int nt = S / VA_KT;
+  const int nt = RAGGED ? (S + VA_KT - 1) / VA_KT : S / VA_KT;
+  // RAGGED, last tile: this lane's keys 16 T + 4 g + r (scores) = its V^T operand elements 4 T + r are real iff 16 T + r < krem
+  const int krem = S - (nt - 1) * VA_KT - 4 * g;
   dma_tile(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
@@ -346,13 +356,30 @@ __global__ __launch_bounds__(512) void vae_attn_kernel(const bf16_t* __restrict_
     }
     // ---- online softmax for query l15 (its 8 keys of this tile in this lane; the rest in lanes l15 + 16 g')
     float tmax = -1e30f;
+    if constexpr (RAGGED) {
 #pragma unroll
-    for (int T = 0; T < 2; ++T)
+      for (int T = 0; T < 2; ++T)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        sc[T][r] *= scale_log2e;
-        tmax = fmaxf(tmax, sc[T][r]);
+        for (int r = 0; r < 4; ++r) sc[T][r] *= scale_log2e;
+      if (t == nt - 1) {
+#pragma unroll
+        for (int T = 0; T < 2; ++T)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) sc[T][r] = 16 * T + r < krem ? sc[T][r] : -1e30f;
       }
+#pragma unroll
+      for (int T = 0; T < 2; ++T)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tmax = fmaxf(tmax, sc[T][r]);
+    } else {
+#pragma unroll
+      for (int T = 0; T < 2; ++T)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          sc[T][r] *= scale_log2e;
+          tmax = fmaxf(tmax, sc[T][r]);
+        }
+    }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 16));
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
     const float m_new = fmaxf(m_run, tmax);
@@ -360,14 +387,30 @@ __global__ __launch_bounds__(512) void vae_attn_kernel(const bf16_t* __restrict_
     m_run = m_new;
     float psum = 0.f;
     float pv[8];
+    u32x4 vkeep = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};   // RAGGED, last tile: the real keys' bits of a V^T fragment
+    if constexpr (RAGGED) {
 #pragma unroll
-    for (int T = 0; T < 2; ++T)
+      for (int e = 0; e < 8; ++e) pv[e] = __builtin_amdgcn_exp2f(sc[e >> 2][e & 3] - m_new);
+      if (t == nt - 1) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float e = __builtin_amdgcn_exp2f(sc[T][r] - m_new);
-        pv[T * 4 + r] = e;
-        psum += e;
+        for (int e = 0; e < 8; ++e) {
+          const bool real = 16 * (e >> 2) + (e & 3) < krem;
+          pv[e] = real ? pv[e] : 0.f;                                     // bf16(0) is +0: the key's P^T element is exactly 0
+          vkeep[e >> 1] &= real ? 0xffffffffu : ~(0xffffu << (16 * (e & 1)));
+        }
       }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) psum += pv[e];
+    } else {
+#pragma unroll
+      for (int T = 0; T < 2; ++T)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = __builtin_amdgcn_exp2f(sc[T][r] - m_new);
+          pv[T * 4 + r] = e;
+          psum += e;
+        }
+    }
     l_run = l_run * alpha + psum;
     if (__any(alpha != 1.0f)) {
 #pragma unroll
@@ -394,8 +437,12 @@ __global__ __launch_bounds__(512) void vae_attn_kernel(const bf16_t* __restrict_
       for (int G = 0; G < 4; ++G) {
         if (G + 1 < 4) rd_v(G + 1, vfr[(G + 1) & 1]);
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
+        for (int e = 0; e < 4; ++e) {
+          if constexpr (RAGGED) {
+            if (t == nt - 1) vfr[G & 1][e] &= vkeep;
+          }
           oacc[G * 4 + e] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vfr[G & 1][e]), pb, oacc[G * 4 + e], 0, 0, 0);
+        }
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -436,7 +483,7 @@ struct VaeCtx {
   bf16_t* ones;                // [1024] bf16 1.0
   float* part;                 // GroupNorm block partials [GN_BLOCKS][C][2]
   float* ab;                   // [2][C]
-  bf16_t *aqk, *avt, *ao;      // attention: [S][2C], [C][S], [S][C]
+  bf16_t *aqk, *avt, *ao;      // attention: [S_pad][2C], [C][S_pad], [S][C]  (S_pad = round_up(S, 64))
   bf16_t* col;                 // encoder: im2col buffer
   void* sk; int64_t sk_bytes;  // GEMM scratch (stream-K flags + partial tiles)
 };
@@ -480,9 +527,18 @@ static int downsample_check(const rf_vae_conv& cv, int H, int W) {
 
 static int attention_check(int C, int S) {
   RF_REQUIRE(C == VA_C, RF_ERR_UNSUPPORTED, "rf_vae: the attention kernel is built for %d channels (got %d)", VA_C, C);
-  RF_REQUIRE(S > 0 && S % 64 == 0, RF_ERR_SHAPE, "rf_vae: attention over %d tokens (need a multiple of 64)", S);
+  RF_REQUIRE(S > 0, RF_ERR_SHAPE, "rf_vae: attention over %d tokens", S);
   return RF_OK;
 }
+
+// RF_VAE_OP_ATTN_CORE / _ATTN_BLOCK: the kernel without a key tail only (the _RAGGED ops and the product path take any S)
+static int attention_whole_tiles_check(int C, int S) {
+  RF_TRY(attention_check(C, S));
+  RF_REQUIRE(S % 64 == 0, RF_ERR_SHAPE, "rf_vae: attention over %d tokens (need a multiple of 64)", S);
+  return RF_OK;
+}
+
+static inline int attn_s_pad(int S) { return (int)round_up(S, 64); }
 
 static int group_norm(VaeCtx& c, const rf_vae_norm& n, const bf16_t* x, bf16_t* y, int H, int W, int C, bool silu, bool compact) {
   RF_TRY(group_norm_check(n, C, c.w->groups));
@@ -595,16 +651,29 @@ static int resnet(VaeCtx& c, const rf_vae_resnet& r, int H, int W) {
   return conv3x3(c, r.conv2, c.T1, c.X, H, W, res);   // out may alias the residual (Ci == Co) -- the epilogue reads before it writes
 }
 
-// out [S][C] = softmax(q k^T / sqrt(C)) v  for qk [S][2C] (q | k), vt [C][S]: the one launch site of vae_attn_kernel
+// out [S][C] = softmax(q k^T / sqrt(C)) v  for qk [S_pad][2C] (q | k), vt [C][S_pad], S_pad = attn_s_pad(S): the one launch site of
+// vae_attn_kernel.  S % 64 == 0 (S_pad == S) runs the instantiation without a key tail; anything else the ragged one, which reads
+// neither the rows S .. of qk nor the columns S .. of vt for a result (their content is the caller's leftovers) and writes rows < S of out.
 static int attention_core(hipStream_t st, const bf16_t* qk, const bf16_t* vt, bf16_t* out, int S, int C) {
   RF_TRY(attention_check(C, S));
-  static bool attr_set = false;
-  if (!attr_set) {
-    RF_CHECK_HIP(hipFuncSetAttribute((const void*)vae_attn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, VA_LDS));
-    attr_set = true;
-  }
+  const int S_pad = attn_s_pad(S);
+  const float scale_log2e = 1.4426950408889634f / sqrtf((float)C);
   ProfScope prof(RF_KC_ATTN, 4.0 * (double)S * S * C, st);
-  hipLaunchKernelGGL(vae_attn_kernel, dim3(S / 64), dim3(512), VA_LDS, st, qk, vt, out, S, 1.4426950408889634f / sqrtf((float)C));
+  if (S_pad == S) {
+    static bool attr_set = false;
+    if (!attr_set) {
+      RF_CHECK_HIP(hipFuncSetAttribute((const void*)vae_attn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, VA_LDS));
+      attr_set = true;
+    }
+    hipLaunchKernelGGL(vae_attn_kernel<false>, dim3(S / 64), dim3(512), VA_LDS, st, qk, vt, out, S, scale_log2e, S);
+  } else {
+    static bool attr_set_ragged = false;
+    if (!attr_set_ragged) {
+      RF_CHECK_HIP(hipFuncSetAttribute((const void*)vae_attn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, VA_LDS));
+      attr_set_ragged = true;
+    }
+    hipLaunchKernelGGL(vae_attn_kernel<true>, dim3(S_pad / 64), dim3(512), VA_LDS, st, qk, vt, out, S, scale_log2e, S_pad);
+  }
   RF_LAUNCH_CHECK();
   return RF_OK;
 }
@@ -622,7 +691,8 @@ static int attention(VaeCtx& c, const rf_vae_attn& a, int H, int W) {
   bf16_t* xn = c.T1;                                               // compact [S][C]
   RF_TRY(group_norm(c, a.norm, c.X, xn, H, W, C, false, true));
   RF_TRY(linear(c, xn, C, a.w_qk, a.b_qk, S, 2 * C, C, c.aqk, 2 * C));
-  RF_TRY(linear(c, (const bf16_t*)a.w_v, C, xn, nullptr, C, S, C, c.avt, S));   // V^T = W_v . xn^T  (operands swapped)
+  // V^T = W_v . xn^T  (operands swapped): S columns at the pitch S_pad; the columns behind them keep what the workspace held
+  RF_TRY(linear(c, (const bf16_t*)a.w_v, C, xn, nullptr, C, S, C, c.avt, attn_s_pad(S)));
   RF_TRY(attention_core(c.st, c.aqk, c.avt, c.ao, S, C));
   RF_TRY(linear(c, c.ao, C, a.w_out, a.b_out, S, C, C, c.T2, C));
   hipLaunchKernelGGL(add_compact_kernel, dim3(grid_for((int64_t)S * (C / 8))), dim3(256), 0, c.st, c.X, c.T2, H, W, C);
@@ -695,9 +765,9 @@ static VaeSizes vae_sizes(const rf_vae_weights* w, int encode, int h, int wd) {
   see(Hm, Wm, Cm);
   z.cap = round_up(cap + VAE_TAIL * 512 * 2, 256);   // + the zeroed tail behind an image (a folded convolution's last row reads up to fold - 1 pixels of it)
   if (w->has_attn) {
-    const int64_t S = (int64_t)Hm * Wm;
-    z.attn_qk = round_up(S * 2 * Cm * 2, 256);
-    z.attn_vt = round_up(S * Cm * 2, 256);
+    const int64_t S = (int64_t)Hm * Wm, S_pad = round_up(S, 64);   // q | k rows and the V^T pitch: whole 64-token groups
+    z.attn_qk = round_up(S_pad * 2 * Cm * 2, 256);
+    z.attn_vt = round_up(S_pad * Cm * 2, 256);
     z.attn_o = round_up(S * Cm * 2, 256);
   }
   z.col = round_up(col, 256);
@@ -806,10 +876,12 @@ static VaeOpSizes vae_op_sizes(const rf_vae_op_desc* d) {
   memset(&z, 0, sizeof(z));
   const int64_t S = (int64_t)d->H * d->W;
   if (d->op == RF_VAE_OP_DOWNSAMPLE) z.col = round_up((int64_t)(d->H / 2) * (d->W / 2 + 2) * 9 * d->conv->cin * 2, 256);
-  if (d->op == RF_VAE_OP_ATTN_BLOCK) {
+  if (d->op == RF_VAE_OP_ATTN_BLOCK || d->op == RF_VAE_OP_ATTN_BLOCK_RAGGED) {
+    const int64_t S_pad = round_up(S, 64);
     z.t = round_up(S * VA_C * 2, 256);          // T1 (compact normalised x) and T2 (compact out-projection)
-    z.aqk = round_up(S * 2 * VA_C * 2, 256);
-    z.avt = z.ao = round_up(S * VA_C * 2, 256);
+    z.aqk = round_up(S_pad * 2 * VA_C * 2, 256);
+    z.avt = round_up(S_pad * VA_C * 2, 256);
+    z.ao = round_up(S * VA_C * 2, 256);
   }
   z.total = round_up(1024 * 2, 256) + round_up((int64_t)GN_BLOCKS * 512 * 2 * 4, 256) + round_up(2 * 512 * 4, 256) + 4096 + (64ll << 20) + z.col + 2 * z.t +
             z.aqk + z.avt + z.ao;
@@ -819,7 +891,7 @@ static VaeOpSizes vae_op_sizes(const rf_vae_op_desc* d) {
 extern "C" int64_t rf_debug_vae_op(const rf_vae_op_desc* d, void* stream) {
   const char* who = "rf_debug_vae_op";
   RF_REQUIRE(d, RF_ERR_NULL, "%s: descriptor NULL", who);
-  RF_REQUIRE(d->op >= RF_VAE_OP_GROUP_NORM && d->op <= RF_VAE_OP_ATTN_BLOCK, RF_ERR_UNSUPPORTED, "%s: op=%d", who, d->op);
+  RF_REQUIRE(d->op >= RF_VAE_OP_GROUP_NORM && d->op <= RF_VAE_OP_ATTN_BLOCK_RAGGED, RF_ERR_UNSUPPORTED, "%s: op=%d", who, d->op);
   RF_REQUIRE(d->H > 0 && d->W > 0 && d->H <= 8192 && d->W <= 8192, RF_ERR_SHAPE, "%s: H=%d W=%d", who, d->H, d->W);
   const int H = d->H, W = d->W, C = d->C;
   switch (d->op) {
@@ -839,13 +911,14 @@ extern "C" int64_t rf_debug_vae_op(const rf_vae_op_desc* d, void* stream) {
       RF_TRY(downsample_check(*d->conv, H, W));
       break;
     case RF_VAE_OP_ATTN_CORE:
-      RF_TRY(attention_check(C, H * W));
+    case RF_VAE_OP_ATTN_CORE_RAGGED:
+      RF_TRY(d->op == RF_VAE_OP_ATTN_CORE ? attention_whole_tiles_check(C, H * W) : attention_check(C, H * W));
       RF_REQUIRE(d->residual, RF_ERR_NULL, "%s: ATTN_CORE without vt (residual)", who);
       break;
-    default:   // RF_VAE_OP_ATTN_BLOCK
+    default:   // RF_VAE_OP_ATTN_BLOCK, RF_VAE_OP_ATTN_BLOCK_RAGGED
       RF_REQUIRE(d->attn, RF_ERR_NULL, "%s: ATTN_BLOCK without attn", who);
       RF_REQUIRE(d->attn->C == C, RF_ERR_SHAPE, "%s: attn->C=%d but C=%d", who, d->attn->C, C);
-      RF_TRY(attention_check(C, H * W));
+      RF_TRY(d->op == RF_VAE_OP_ATTN_BLOCK ? attention_whole_tiles_check(C, H * W) : attention_check(C, H * W));
       RF_TRY(attention_weights_check(*d->attn));
       RF_TRY(group_norm_check(d->attn->norm, C, d->groups));
       break;
@@ -854,7 +927,7 @@ extern "C" int64_t rf_debug_vae_op(const rf_vae_op_desc* d, void* stream) {
   if (!d->ws || !d->ws->base) return z.total;
   RF_REQUIRE(aligned16(d->ws->base) && d->ws->bytes >= z.total, RF_ERR_WORKSPACE, "%s: workspace %lld < required %lld bytes (or not 16-byte aligned)", who,
              (long long)d->ws->bytes, (long long)z.total);
-  RF_REQUIRE(d->out && (d->in || d->op == RF_VAE_OP_ATTN_BLOCK), RF_ERR_NULL, "%s: NULL tensor", who);
+  RF_REQUIRE(d->out && (d->in || d->op == RF_VAE_OP_ATTN_BLOCK || d->op == RF_VAE_OP_ATTN_BLOCK_RAGGED), RF_ERR_NULL, "%s: NULL tensor", who);
   RF_REQUIRE(aligned16(d->in) && aligned16(d->out) && aligned16(d->residual), RF_ERR_ALIGN, "%s: tensors must be 16-byte aligned", who);
 
   rf_vae_weights wt;
@@ -882,7 +955,8 @@ extern "C" int64_t rf_debug_vae_op(const rf_vae_op_desc* d, void* stream) {
     case RF_VAE_OP_CONV3X3: return conv3x3(c, *d->conv, in, out, H, W, (const bf16_t*)d->residual);
     case RF_VAE_OP_UPSAMPLE2X: return upsample2x(c, in, out, H, W, C);
     case RF_VAE_OP_DOWNSAMPLE: return downsample(c, *d->conv, in, out, H, W);
-    case RF_VAE_OP_ATTN_CORE: return attention_core(c.st, in, (const bf16_t*)d->residual, out, H * W, C);
+    case RF_VAE_OP_ATTN_CORE:
+    case RF_VAE_OP_ATTN_CORE_RAGGED: return attention_core(c.st, in, (const bf16_t*)d->residual, out, H * W, C);
     default: return attention(c, *d->attn, H, W);
   }
 }

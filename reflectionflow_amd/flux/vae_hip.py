@@ -161,15 +161,11 @@ class HipVAE:
 
     def check_geometry(self, height: int, width: int, what: str = "image") -> None:
         """Raise NOW (before a search has spent minutes denoising) if an image of height x width pixels cannot go through this VAE:
-        sides must be multiples of the down-scaling factor, and the mid-block attention kernel needs (h / scale)(w / scale) % 64 == 0
-        latent pixels.  The torch AutoencoderKL it replaces takes any size; callers with odd sizes keep the torch module
-        (do not call pipe.enable_hip_vae())."""
+        its sides must be multiples of the down-scaling factor.  Nothing else is asked of the size: the mid-block attention kernel
+        masks the key tail of a latent-pixel count that is not a multiple of 64 (csrc/vae.hip, vae_attn_kernel<true>)."""
         s = self.scale
         if height % s or width % s:
             raise RFError(f"HipVAE: {what} {height}x{width}: sides must be multiples of {s}")
-        if (self._dec.has_attn or self._enc.has_attn) and ((height // s) * (width // s)) % 64:
-            raise RFError(f"HipVAE: {what} {height}x{width} has {(height // s) * (width // s)} latent pixels; the mid-block attention "
-                          "kernel needs a multiple of 64 (e.g. sides that are multiples of 64 pixels)")
 
     def to(self, *a, **k):                                  # pipeline.to(device) walks its parts
         return self
