@@ -587,7 +587,7 @@ int rf_clip_vision_encode(const rf_clip_vision_weights* w, const void* patches, 
  * returns RF_ERR_SHAPE from the size query and the encode call alike.  A hidden width that is no multiple
  * of the GEMM's 64-element K-tile (test-size towers; 1280 is one): every weight whose K axis is `hidden` (w_qk, w_v, w_o, w_fc1,
  * proj) is passed with row pitch round_up(hidden, 64), zero beyond `hidden`.  Other head dims / activations: RF_ERR_UNSUPPORTED. */
-enum { RF_CLIP_ACT_QUICK_GELU = 0, RF_CLIP_ACT_GELU = 1 };
+enum { RF_CLIP_ACT_QUICK_GELU = 0, RF_CLIP_ACT_GELU = 1, RF_CLIP_ACT_GELU_TANH = 2 /* the SigLIP entry points' own; refused in rf_clip_tower_opts */ };
 typedef struct rf_clip_tower_opts { int32_t head_dim; int32_t act; } rf_clip_tower_opts;
 int64_t rf_clip_text_workspace_bytes_opts(const rf_clip_weights* w, const rf_clip_tower_opts* o, int32_t B, int32_t S);
 int rf_clip_text_encode_opts(const rf_clip_weights* w, const rf_clip_tower_opts* o, const int32_t* ids, int32_t B, int32_t S, const int32_t* eos_pos,
@@ -616,6 +616,86 @@ int rf_text_attention(int32_t head_dim, int32_t qi, int32_t stream_keys, const v
 /* scores[b] = exp(logit_scale) * <img_b / |img_b|, txt / |txt|> in fp32 (img [B][P], txt [P] bf16; logit_scale = the model's
  * log-domain parameter); one workgroup per row, fixed reduction order */
 int rf_clip_score(const void* img, const void* txt, float logit_scale, float* scores, int32_t B, int32_t P, void* stream);
+
+/* SigLIP building blocks (google/siglip-so400m-patch14-384: hidden 1152 = 16 heads x 72, 729 tokens at 384 px; also the vision tower
+ * inside NVILA / VILA).  Additive to ABI v17: new symbols only, every entry point above answers as it did.
+ *
+ * rf_text_attention80: rf_text_attention's contract at head dim 80 -- operands, bias, masking, qi and the bitwise guarantees as
+ * documented there, with head h in columns 80 h ... of q / k / out and vt [80 heads][ldvt].  A head narrower than 80 channels (72)
+ * is served exactly by a binding that zero-pads it: q, k, v channels d .. 79 of every head zero give the true scores and output
+ * channels d .. 79 exactly 0.
+ *   stream_keys  0 = K and V^T resident in the LDS up to S_pad = 480 (the launch the ViT-H/14 towers make), streamed through it in
+ *                96-key chunks with an online softmax beyond, up to S_pad = 2048; 1 = streamed at any S_pad. */
+int rf_text_attention80(int32_t qi, int32_t stream_keys, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
+                        const float* bias, int64_t bias_hs, void* out, int64_t ldo, int32_t heads, int32_t B, int32_t S, int32_t S_pad, float scale,
+                        void* stream);
+/* SigLIP's pairwise sigmoid: scores[b] = sigmoid(exp(logit_scale) * <img_b / |img_b|, txt / |txt|> + logit_bias) in fp32, a
+ * calibrated match probability, and labels[b] = scores[b] >= threshold (int32 1 | 0; labels may be NULL).  img [B][P], txt [P] bf16;
+ * one workgroup per row, fixed reduction order (rf_clip_score's). */
+int rf_siglip_score(const void* img, const void* txt, float logit_scale, float logit_bias, float threshold, float* scores, int32_t* labels, int32_t B,
+                    int32_t P, void* stream);
+
+/* transformers' SiglipVisionModel (pooler_output) and SiglipTextModel (pooler_output) on the CLIP towers' encoder layers.
+ * Packing, the binding's job (flux/text_hip.py) and exact: a head of d <= 80 channels occupies 80 (inner = 80 heads): rows 80 h + d ..
+ * 80 h + 79 of q_proj / k_proj / v_proj and their biases are zero, as are the matching columns of out_proj; 1/sqrt(d) of the TRUE d is
+ * folded into q; the v bias into b_o.  So a layer is an rf_clip_layer with w_qk [2 inner][Dp], b_qk [2 inner], w_v [inner][Dp],
+ * w_o [hidden][Ip], Dp / Ip = hidden / inner rounded up to 64, zero beyond.  `inter` is the intermediate size rounded up to 64 with
+ * zero fc1 rows / biases and zero fc2 columns (gelu(0) = 0).  LayerNorms are (weight - 1, bias) pairs; eps is the config's (1e-6).
+ * The activation is gelu_pytorch_tanh: the fc1 GEMM's output is rounded to bf16, the RF_CLIP_ACT_GELU_TANH row kernel forms
+ * gelu_tanh of it in fp32 and rounds once more (nn.Linear then F.gelu on a bf16 tensor).
+ * Attention: S_pad = round_up(tokens, 32) rows per sequence, padded key columns masked with -inf; keys resident in the LDS up to
+ * S_pad = 480, streamed beyond (rf_text_attention80's rule).  Every GEMM runs on the CLIP vision tower's one pinned schedule, so a
+ * row's embedding does not depend on B.  Limits: 1 <= B <= 64, tokens <= 2048, 80 heads <= 4096, hidden % 8 == 0, head_dim % 8 == 0. */
+/* rf_clip_preprocess's input contract and im2col output with SiglipImageProcessor's pipeline: level = rint(255 clamp(a v + b, 0, 1));
+ * PIL resize((size, size), BICUBIC) on the 8-bit levels, BOTH axes straight to `size` (no shortest-edge rule, no crop; up- and
+ * down-scaling), horizontal pass first, rounded and clipped to 8 bits, then the vertical pass; (v / 255 - 0.5) / 0.5 rounded to bf16.
+ * The patch convolution is "valid": rows / columns >= (size / patch) * patch of the resized image reach no patch (so400m/14 at 384 px:
+ * 27 x 27 patches of 378 pixels), so patches is [B * (size / patch)^2][K_pad].  H, W <= 8192, patch <= size <= 512. */
+int rf_siglip_preprocess(const void* img, int64_t s_img, int64_t s_row, int64_t s_pix, int64_t s_ch, int32_t B, int32_t H, int32_t W, float a,
+                         float b, int32_t size, int32_t patch, void* patches, void* stream);
+typedef struct rf_siglip_vision_weights {
+  int32_t layers, hidden, heads, head_dim;   /* head_dim: the true d = hidden / heads <= 80 (the pooling head's attention runs at it) */
+  int32_t inter, image_size, patch, mask_S;  /* tokens T = (image_size / patch)^2, the quotient floored (384 / 14 = 27); mask_S = round_up(T, 32) */
+  float eps; int32_t _pad;
+  const void* patch_w;                       /* patch_embedding.weight as [hidden][K_pad], as rf_clip_vision_weights */
+  const void* patch_b;                       /* patch_embedding.bias [hidden] */
+  const void* pos_embed;                     /* position_embedding.weight [T][hidden]; no class token, no pre-LN */
+  const void *post_ln_scale, *post_ln_shift;
+  const float* mask;                         /* [mask_S][mask_S] fp32: 0 in columns < T, -inf beyond; may be NULL when T == mask_S */
+  const rf_clip_layer* layer;                /* HOST array [layers], packed as above */
+  /* SiglipMultiheadAttentionPoolingHead: one probe query per head over the T post-layernormed tokens */
+  const void *w_kv, *b_kv;                   /* head.attention.in_proj_weight[hidden : 3 hidden] as [2 hidden][Dp], in_proj_bias[hidden:] */
+  const float* probe_q;                      /* fp32 [hidden]: (probe W_q^T + b_q) / sqrt(d), input-independent, computed by the binding */
+  const void *w_po, *b_po;                   /* head.attention.out_proj [hidden][Dp], [hidden] */
+  const void *hln_scale, *hln_shift;         /* head.layernorm */
+  const void *w_hfc1, *b_hfc1, *w_hfc2, *b_hfc2;   /* head.mlp: [inter][Dp], [inter], [hidden][inter], [hidden] */
+} rf_siglip_vision_weights;
+int64_t rf_siglip_vision_workspace_bytes(const rf_siglip_vision_weights* w, int32_t B);
+/* patches [B * T][K_pad] (rf_siglip_preprocess / rf_clip_preprocess layout) -> pooled [B][hidden] bf16 */
+int rf_siglip_vision_encode(const rf_siglip_vision_weights* w, const void* patches, int32_t B, void* pooled, const rf_workspace* ws, void* stream);
+
+/* The pooling head's probe attention as one launch on caller buffers (a binding that runs a pooling head of its own; the kernel-level
+ * tests): one fp32 query per head (q [heads * head_dim], 1/sqrt(head_dim) already folded in) over T keys at the TRUE head dim, fp32
+ * softmax, fixed reduction order, bitwise repeatable.  k, v: bf16, image b's token t in row b * seq_rows + t of pitch ldk / ldv
+ * (elements, multiples of 8; k, v 16-byte aligned), head h in columns h * head_dim ..; out [B][ldo] bf16.  head_dim % 8 == 0, <= 80;
+ * T <= 2048; B <= 64; heads * 80 <= 4096.  Everything is checked before the launch. */
+int rf_siglip_probe_attention(const float* q, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out, int64_t ldo, int32_t heads,
+                              int32_t head_dim, int32_t B, int32_t T, int32_t seq_rows, void* stream);
+
+typedef struct rf_siglip_text_weights {
+  int32_t layers, hidden, heads, head_dim;
+  int32_t inter, vocab, max_pos, proj_dim;   /* proj_dim: rows of head.weight (projection_size), % 8 == 0 */
+  float eps; int32_t mask_S;                 /* mask_S: the S_pad the mask is built for (ignored when mask is NULL) */
+  const void *tok_embed, *pos_embed;
+  const void *final_ln_scale, *final_ln_shift;
+  const void *head_w, *head_b;               /* head [proj_dim][Dp], [proj_dim] */
+  const float* mask;                         /* NO causal mask: NULL when S % 32 == 0 (S = 64 for every published checkpoint), else
+                                                [S_pad][S_pad] with -inf in the key columns >= S */
+  const rf_clip_layer* layer;
+} rf_siglip_text_weights;
+int64_t rf_siglip_text_workspace_bytes(const rf_siglip_text_weights* w, int32_t B, int32_t S);
+/* ids [B][S] int32 -> pooled [B][proj_dim] bf16 = head(final_layer_norm(x)[:, S - 1]) */
+int rf_siglip_text_encode(const rf_siglip_text_weights* w, const int32_t* ids, int32_t B, int32_t S, void* pooled, const rf_workspace* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Round hand-off of the reflection search (tts_reflectionflow.py:273-279: a selected candidate's PNG is re-opened,

@@ -188,7 +188,23 @@ class rf_clip_tower_opts(C.Structure):
 
 
 RF_CLIP_ACT_QUICK_GELU, RF_CLIP_ACT_GELU = 0, 1
+RF_CLIP_ACT_GELU_TANH = 2          # the SigLIP entry points' own activation; rf_clip_tower_opts refuses it
 CLIP_ACTS = {"quick_gelu": RF_CLIP_ACT_QUICK_GELU, "gelu": RF_CLIP_ACT_GELU}
+
+
+class rf_siglip_vision_weights(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("layers", "hidden", "heads", "head_dim", "inter", "image_size", "patch", "mask_S")] + \
+               [("eps", C.c_float), ("_pad", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("patch_w", "patch_b", "pos_embed", "post_ln_scale", "post_ln_shift", "mask")] + \
+               [("layer", C.POINTER(rf_clip_layer))] + \
+               [(n, C.c_void_p) for n in ("w_kv", "b_kv", "probe_q", "w_po", "b_po", "hln_scale", "hln_shift", "w_hfc1", "b_hfc1", "w_hfc2", "b_hfc2")]
+
+
+class rf_siglip_text_weights(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("layers", "hidden", "heads", "head_dim", "inter", "vocab", "max_pos", "proj_dim")] + \
+               [("eps", C.c_float), ("mask_S", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("tok_embed", "pos_embed", "final_ln_scale", "final_ln_shift", "head_w", "head_b", "mask")] + \
+               [("layer", C.POINTER(rf_clip_layer))]
 
 
 # every symbol include/rf_flux.h (the product ABI) declares: (restype, argtypes)
@@ -251,6 +267,21 @@ _SIGS = {
     # (head_dim, qi, stream_keys, q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, heads, B, S, S_pad, scale, stream)
     "rf_text_attention": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64,
                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
+    # the same contract at head dim 80 (SigLIP so400m: heads of 72 zero-padded to 80); keys beyond 480 (or stream_keys = 1) are streamed
+    # (qi, stream_keys, q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, heads, B, S, S_pad, scale, stream)
+    "rf_text_attention80": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64,
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
+    # SigLIP towers (csrc/siglip.hip) and SiglipImageProcessor (rf_clip_preprocess's arguments)
+    "rf_siglip_preprocess": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                       C.c_int32, C.c_int32, _P, _P]),
+    "rf_siglip_vision_workspace_bytes": (C.c_int64, [C.POINTER(rf_siglip_vision_weights), C.c_int32]),
+    "rf_siglip_vision_encode": (C.c_int, [C.POINTER(rf_siglip_vision_weights), _P, C.c_int32, _P, C.POINTER(rf_workspace), _P]),
+    "rf_siglip_text_workspace_bytes": (C.c_int64, [C.POINTER(rf_siglip_text_weights), C.c_int32, C.c_int32]),
+    "rf_siglip_text_encode": (C.c_int, [C.POINTER(rf_siglip_text_weights), _P, C.c_int32, C.c_int32, _P, C.POINTER(rf_workspace), _P]),
+    # (q, k, ldk, v, ldv, out, ldo, heads, head_dim, B, T, seq_rows, stream)
+    "rf_siglip_probe_attention": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    # (img, txt, logit_scale, logit_bias, threshold, scores, labels, B, P, stream)
+    "rf_siglip_score": (C.c_int, [_P, _P, C.c_float, C.c_float, C.c_float, _P, _P, C.c_int32, C.c_int32, _P]),
     # round hand-off of the reflection search (csrc/image_handoff.hip)
     "rf_image_levels": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rf_pil_resize_to_vae_input": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32,

@@ -133,6 +133,123 @@ __global__ __launch_bounds__(256) void clip_preprocess_kernel(const bf16_t* __re
   }
 }
 
+// ---- SiglipImageProcessor: PIL's 8-bit resample, exactly ---------------------------------------------------------------------------
+// Pillow's 8-bit resampler is INTEGER arithmetic (Resample.c): per axis the bicubic weights are formed in double, normalised, turned
+// into 22-bit fixed-point coefficients (round half away from zero), and a pass gives clip8(((1 << 21) + sum level * coef) >> 22).
+// The float filter of clip_preprocess_kernel above differs from it by one level in a few percent of the pixels, so SigLIP's
+// preprocessing, which is held to PIL level for level, restates Pillow's own arithmetic -- the arithmetic image_handoff.hip's
+// rf_pil_resize_to_vae_input runs from host-built tables, here with the coefficients recomputed per tap in double on the device (no
+// table: the entry point has no workspace; +, *, / in double are IEEE on both sides, contraction is off).
+__device__ __forceinline__ double pil_bicubic(double x) {
+#pragma clang fp contract(off)
+  const double a = -0.5;
+  if (x < 0.0) x = -x;
+  if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+  if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+  return 0.0;
+}
+struct PilWin { int lo, n; double center, ss, ww; };
+__device__ __forceinline__ PilWin pil_window(int i, int in_size, int out_size) {   // precompute_coeffs, one output pixel
+#pragma clang fp contract(off)
+  PilWin r;
+  const double scale = (double)in_size / out_size;
+  const double filterscale = scale < 1.0 ? 1.0 : scale;
+  const double support = 2.0 * filterscale;
+  r.center = (i + 0.5) * scale;
+  r.ss = 1.0 / filterscale;
+  r.lo = (int)(r.center - support + 0.5);
+  if (r.lo < 0) r.lo = 0;
+  int hi = (int)(r.center + support + 0.5);
+  if (hi > in_size) hi = in_size;
+  r.n = hi - r.lo;
+  r.ww = 0.0;
+  for (int x = 0; x < r.n; ++x) r.ww += pil_bicubic((x + r.lo - r.center + 0.5) * r.ss);
+  return r;
+}
+__device__ __forceinline__ int pil_coef(const PilWin& w, int x) {   // normalize_coeffs_8bpc of tap x
+#pragma clang fp contract(off)
+  double k = pil_bicubic((x + w.lo - w.center + 0.5) * w.ss);
+  if (w.ww != 0.0) k /= w.ww;
+  return k < 0 ? (int)(-0.5 + k * 4194304.0) : (int)(0.5 + k * 4194304.0);
+}
+__device__ __forceinline__ int pil_clip8(int ss) { return min(max(ss >> 22, 0), 255); }
+
+// clip_preprocess_kernel's structure (one workgroup per output row and image, the vertical window's source rows staged one at a time
+// in LDS, thread x owns output columns x + 256 n, im2col scatter, K padding zeroed by the rows with ky == 0) with the arithmetic above:
+// both axes go straight to `size`, the horizontal pass of a source row is clipped to 8 bits before the vertical pass accumulates it,
+// then (v / 255 - 0.5) / 0.5 in fp32, one rounding to bf16.  The patch convolution is "valid": of the size x size image only the first
+// used = (size / patch) * patch rows and columns reach a patch (so400m/14 at 384 px: 27 x 14 = 378), the grid has `used` rows.
+template <int NX>
+__global__ __launch_bounds__(256) void siglip_preprocess_kernel(const bf16_t* __restrict__ img, int64_t s_img, int64_t s_row, int64_t s_pix, int64_t s_ch,
+                                                                int H, int W, float a, float b, int size, int used, int patch, int K_pad,
+                                                                bf16_t* __restrict__ out) {
+#pragma clang fp contract(off)
+  extern __shared__ int lrow[];   // [3][span]
+  const int y = blockIdx.x, bi = blockIdx.y, tid = threadIdx.x;
+  const bf16_t* src = img + (int64_t)bi * s_img;
+  const PilWin vy = pil_window(y, H, size);
+  const PilWin wx0 = pil_window(0, W, size), wx1 = pil_window(used - 1, W, size);
+  const int sx0 = wx0.lo, span = wx1.lo + wx1.n - sx0;
+  bool act[NX];
+  PilWin wx[NX];
+  int acc[NX][3];
+#pragma unroll
+  for (int n = 0; n < NX; ++n) {
+    act[n] = tid + 256 * n < used;
+    wx[n] = pil_window(act[n] ? tid + 256 * n : 0, W, size);
+    acc[n][0] = acc[n][1] = acc[n][2] = 1 << 21;
+  }
+  const bool ch_fast = s_ch <= s_pix;
+  for (int j = 0; j < vy.n; ++j) {
+    const int yy = vy.lo + j;
+    __syncthreads();
+    for (int idx = tid; idx < 3 * span; idx += 256) {
+      int p, c;
+      if (ch_fast) { p = idx / 3; c = idx - 3 * p; }
+      else { c = idx / span; p = idx - c * span; }
+      const float v = bf2f(src[(int64_t)yy * s_row + (int64_t)(sx0 + p) * s_pix + (int64_t)c * s_ch]);
+      const float u = fminf(fmaxf(a * v + b, 0.0f), 1.0f);
+      lrow[c * span + p] = (int)rintf(u * 255.0f);                 // the PNG's 8-bit level (numpy's round: half to even)
+    }
+    __syncthreads();
+    const int cy = pil_coef(vy, j);
+#pragma unroll
+    for (int n = 0; n < NX; ++n) {
+      if (act[n]) {
+        const int* r = lrow + (wx[n].lo - sx0);
+        int h[3] = {1 << 21, 1 << 21, 1 << 21};
+        for (int i = 0; i < wx[n].n; ++i) {
+          const int k = pil_coef(wx[n], i);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) h[c] += r[c * span + i] * k;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[n][c] += pil_clip8(h[c]) * cy;   // PIL's 8-bit intermediate image
+      }
+    }
+  }
+  const int gp = used / patch, py = y / patch, ky = y - py * patch, pp = patch * patch;
+#pragma unroll
+  for (int n = 0; n < NX; ++n) {
+    if (act[n]) {
+      const int x = tid + 256 * n, px = x / patch, kx = x - px * patch;
+      bf16_t* o = out + ((int64_t)bi * gp * gp + (int64_t)py * gp + px) * K_pad + ky * patch + kx;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float v = (float)pil_clip8(acc[n][c]) * (1.0f / 255.0f);
+        o[c * pp] = f2bf((v - 0.5f) / 0.5f);
+      }
+    }
+  }
+  if (ky == 0) {
+    const int npad = K_pad - 3 * pp;
+    for (int idx = tid; idx < gp * npad; idx += 256) {
+      const int px = idx / npad, k = 3 * pp + (idx - px * npad);
+      out[((int64_t)bi * gp * gp + (int64_t)py * gp + px) * K_pad + k] = f2bf(0.0f);
+    }
+  }
+}
+
 // ---- token assembly: X[b * S_pad + t] = class + pos[0] (t = 0) | patch row t - 1 + pos[t] (t < T) | 0; D % 8 == 0 ------------------
 __global__ __launch_bounds__(256) void clip_tokens_kernel(const bf16_t* __restrict__ P, const bf16_t* __restrict__ cls, const bf16_t* __restrict__ pos,
                                                           bf16_t* __restrict__ X, int np, int S_pad, int n_rows, int D) {
@@ -175,6 +292,35 @@ __global__ __launch_bounds__(256) void clip_score_kernel(const bf16_t* __restric
     const float st = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
     const float d = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
     scores[b] = expf(logit_scale) * (d / (sqrtf(si) * sqrtf(st)));
+  }
+}
+
+// SigLIP's pairwise sigmoid on clip_score_kernel's reduction (same order, a kernel of its own: clip_score_kernel's results are pinned):
+// p = 1 / (1 + exp(-(exp(logit_scale) * cos + logit_bias))), label = p >= threshold
+__global__ __launch_bounds__(256) void siglip_score_kernel(const bf16_t* __restrict__ img, const bf16_t* __restrict__ txt, float logit_scale, float logit_bias,
+                                                           float threshold, float* __restrict__ scores, int32_t* __restrict__ labels, int P) {
+  __shared__ float red[3][4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const bf16_t* r = img + (int64_t)b * P;
+  float ii = 0.0f, tt = 0.0f, it = 0.0f;
+  for (int p = tid; p < P; p += 256) {
+    const float x = bf2f(r[p]), t = bf2f(txt[p]);
+    ii += x * x; tt += t * t; it += x * t;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    ii += __shfl_xor(ii, o); tt += __shfl_xor(tt, o); it += __shfl_xor(it, o);
+  }
+  if (lane == 0) { red[0][w] = ii; red[1][w] = tt; red[2][w] = it; }
+  __syncthreads();
+  if (tid == 0) {
+    const float si = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    const float st = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    const float d = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
+    const float z = expf(logit_scale) * (d / (sqrtf(si) * sqrtf(st))) + logit_bias;
+    const float p = 1.0f / (1.0f + expf(-z));
+    scores[b] = p;
+    if (labels) labels[b] = p >= threshold ? 1 : 0;
   }
 }
 
@@ -278,6 +424,46 @@ extern "C" int rf_clip_score(const void* img, const void* txt, float logit_scale
   hipStream_t st = (hipStream_t)stream;
   ProfScope prof(RF_KC_ROWOP, (double)(B + 1) * P * 2, st);
   hipLaunchKernelGGL(clip_score_kernel, dim3(B), dim3(256), 0, st, (const bf16_t*)img, (const bf16_t*)txt, logit_scale, scores, P);
+  RF_LAUNCH_CHECK();
+  return RF_OK;
+}
+
+extern "C" int rf_siglip_score(const void* img, const void* txt, float logit_scale, float logit_bias, float threshold, float* scores, int32_t* labels,
+                               int32_t B, int32_t P, void* stream) {
+  RF_REQUIRE(img && txt && scores, RF_ERR_NULL, "rf_siglip_score: NULL tensor");
+  RF_REQUIRE(B > 0 && P > 0, RF_ERR_SHAPE, "rf_siglip_score: B=%d P=%d", B, P);
+  RF_REQUIRE(threshold >= 0.0f && threshold <= 1.0f, RF_ERR_SHAPE, "rf_siglip_score: threshold=%g (a probability, 0 .. 1)", (double)threshold);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope prof(RF_KC_ROWOP, (double)(B + 1) * P * 2, st);
+  hipLaunchKernelGGL(siglip_score_kernel, dim3(B), dim3(256), 0, st, (const bf16_t*)img, (const bf16_t*)txt, logit_scale, logit_bias, threshold, scores, labels, P);
+  RF_LAUNCH_CHECK();
+  return RF_OK;
+}
+
+// SiglipImageProcessor on the device: rf_clip_preprocess's input contract and im2col output with SigLIP's pipeline -- 8-bit levels, PIL
+// resize((size, size), BICUBIC) of both axes straight to `size` (horizontal pass first, rounded and clipped to 8 bits, then the
+// vertical pass; up- and down-scaling), (v / 255 - 0.5) / 0.5, bf16.  siglip_preprocess_kernel: Pillow's integer arithmetic.
+extern "C" int rf_siglip_preprocess(const void* img, int64_t s_img, int64_t s_row, int64_t s_pix, int64_t s_ch, int32_t B, int32_t H, int32_t W, float a,
+                                    float b, int32_t size, int32_t patch, void* patches, void* stream) {
+  RF_REQUIRE(img && patches, RF_ERR_NULL, "rf_siglip_preprocess: NULL tensor");
+  RF_REQUIRE(B > 0 && H > 0 && W > 0 && H <= CP_MAX_SIDE && W <= CP_MAX_SIDE, RF_ERR_SHAPE, "rf_siglip_preprocess: B=%d H=%d W=%d (sides 1 .. %d)", B, H,
+             W, CP_MAX_SIDE);
+  RF_REQUIRE(size > 0 && size <= CP_MAX_SIZE && patch > 0 && patch <= size, RF_ERR_SHAPE, "rf_siglip_preprocess: size=%d patch=%d (patch <= size <= %d)", size,
+             patch, CP_MAX_SIZE);
+  const int used = size / patch * patch;   // the "valid" patch convolution drops the rest (384 = 27 x 14 + 6)
+  RF_REQUIRE(s_row > 0 && s_pix > 0 && s_ch > 0 && (B == 1 || s_img > 0), RF_ERR_SHAPE, "rf_siglip_preprocess: strides must be positive");
+  const int K_pad = (int)round_up(3 * patch * patch, 64);
+  static bool attr = false;
+  if (!attr) {
+    RF_CHECK_HIP(hipFuncSetAttribute((const void*)siglip_preprocess_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * CP_MAX_SIDE * 4));
+    RF_CHECK_HIP(hipFuncSetAttribute((const void*)siglip_preprocess_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * CP_MAX_SIDE * 4));
+    attr = true;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope prof(RF_KC_ROWOP, (double)B * size * size * 3 * 2, st);
+  auto* const kern = size <= 256 ? siglip_preprocess_kernel<1> : siglip_preprocess_kernel<2>;
+  hipLaunchKernelGGL(kern, dim3(used, B), dim3(256), 3 * W * 4, st, (const bf16_t*)img, s_img, s_row, s_pix, s_ch, H, W, a, b, size, used, patch, K_pad,
+                     (bf16_t*)patches);
   RF_LAUNCH_CHECK();
   return RF_OK;
 }

@@ -14,6 +14,8 @@
 //   * attn80_kernel: the same attention at head dim 80 (the ViT-H/14 towers of PickScore / HPSv2 / LAION CLIP-H), keys <= 480;
 //   * attn64_stream_kernel: head dim 64 with 513 .. 2048 keys (ViT-L/14 at 336 px: 577 tokens): K / V^T chunks of 128 keys double-buffered
 //     through the LDS, online softmax;
+//   * attn80_stream_kernel: the same at head dim 80 with 96-key chunks, up to 2048 keys (SigLIP so400m/14 at 384 px: 729 tokens of
+//     head dim 72 zero-padded to 80), reached through rf_text_attention80 and the SigLIP towers (siglip.hip) only;
 //   * row kernels (HBM-bound, 16-byte accesses): embedding gather (+ position rows), T5 RMS norm, gelu_new(a) * b, quick_gelu, gelu (erf).
 #include "common.hpp"
 #include "text_internal.hpp"
@@ -97,6 +99,9 @@ __global__ __launch_bounds__(256) void geglu_rows_kernel(const bf16_t* __restric
 
 // A CLIP tower's MLP activation, in place.  quick_gelu: x * sigmoid(1.702 x).  gelu (transformers' "gelu", the ViT-H towers):
 // x * 0.5 * (1 + erf(x / sqrt(2))) in fp32, one rounding to bf16 -- the operation order of torch.nn.functional.gelu on a bf16 tensor.
+// gelu_pytorch_tanh (RF_CLIP_ACT_GELU_TANH, the SigLIP towers; the CLIP entry points refuse it): the fc1 GEMM stores acc + bias
+// rounded to bf16, this kernel forms gelu_tanh of that in fp32 and rounds to bf16 once -- nn.Linear then F.gelu(approximate="tanh")
+// on a bf16 tensor -- rather than the GEMM's RF_EPI_GELU, which would skip the first rounding.
 // A row kernel of its own, not a GEMM epilogue: the tower runs once per round, not per step.
 template <int ACT>   // rf_clip_act
 __global__ __launch_bounds__(256) void clip_act_kernel(bf16_t* __restrict__ x, int64_t n8) {
@@ -107,6 +112,7 @@ __global__ __launch_bounds__(256) void clip_act_kernel(bf16_t* __restrict__ x, i
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     if constexpr (ACT == RF_CLIP_ACT_GELU) a[i] = a[i] * 0.5f * (1.0f + erff(a[i] * 0.70710678118654752440f));
+    else if constexpr (ACT == RF_CLIP_ACT_GELU_TANH) a[i] = gelu_tanh(a[i]);
     else a[i] = a[i] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * a[i]));
   }
   *(u32x4*)(x + idx * 8) = pack8(a);
@@ -260,8 +266,8 @@ __global__ __launch_bounds__(256) void attn64_kernel(const bf16_t* __restrict__ 
 //     different chunks.  (attn64_kernel's pitch S_pad * 2 + 16 is 2-way under the same model.)
 //   * PV: 5 output tiles of 16 channels, P in registers.
 //   * LDS budget: S_pad * 160 + 80 * 64 * (m | 1) bytes: 92,160 B at S_pad = 288 (257 tokens of ViT-H/14 at 224 px), 153,600 B at
-//     S_pad = 480 = TA80_MAXS, the largest multiple of 32 that fits a CU's 160 KiB (512 keys would need 168,960 B).  Larger towers
-//     are refused by the entry points; there is no streaming-keys variant.
+//     S_pad = 480 = TA80_MAXS, the largest multiple of 32 that fits a CU's 160 KiB (512 keys would need 168,960 B).  The CLIP entry
+//     points refuse larger towers; attn80_stream_kernel below streams the keys for rf_text_attention80 and the SigLIP towers.
 //   * q scale: the binding folds 1/sqrt(80) into the q weights and bias, `scale` is 1.
 // tests/test_clip_h_cpu.py restates the three fragment-read address formulas against the bank model.
 constexpr int TA80_NT = TA80_MAXS / 16;
@@ -584,6 +590,210 @@ __global__ __launch_bounds__(256, 2) void attn64_stream_kernel(const bf16_t* __r
   }
 }
 
+// ---- attention, head dim 80, keys streamed through the LDS (S_pad <= TAS80_MAXS) ------------------------------------------------------
+// attn80_kernel's operand contract word for word (q, k [S_pad][ld] with head h in columns 80 h .., vt [heads * 80][ldvt], bias fp32
+// [.][S_pad][S_pad] with head stride bias_hs or NULL, out [S][ldo], scale, S_pad % 32 == 0, blockIdx.z = sequence, rows / keys >= S
+// masked by the bias alone, rows >= S not written) for towers with more than TA80_MAXS = 480 keys: SigLIP so400m/14 at 384 px has 729
+// tokens (S_pad 736) of 16 heads x 72 channels, which its binding zero-pads to 80.  Built as attn64_stream_kernel is; decisions:
+//   * Chunks of TAS80_CK = 96 keys, two LDS buffers.  A buffer is attn80_kernel's image of a 96-key head: K rows of 160 B as they lie
+//     in memory (unswizzled: row r starts at slot 10 r mod 16, conflict-free as argued above attn80_kernel), V^T rows of pitch
+//     64 * m bytes with m = 96 / 32 = 3, which is odd WITHOUT a padding block, 16-byte chunk g of a key block at g ^ {0, 2, 3, 1}[(d & 15) >> 2],
+//     key slots permuted (slot(key) = 8 (key%16 / 4) + 4 (key / 16) + key % 4).  Both buffers start on a multiple of 256 B, so the
+//     fragment-read formulas are the resident kernel's at S_pad = 96 and conflict-free in either buffer.
+//   * LDS budget: 2 x (96 * 160 + 80 * 192) = 61,440 B whatever S_pad is: two workgroups per CU (160 KiB / 60 KiB), i.e. two waves
+//     per SIMD, as __launch_bounds__(256, 2) asks of the register allocator, like the head-dim-64 streaming kernel.  The alternative,
+//     128 keys per chunk, needs m = 4 -> 5 (a padding block), 2 x 46,080 = 92,160 B = ONE workgroup per CU, 8 instead of 6 score
+//     tiles in registers per query tile and three quarters of the barriers.  The choice is by that arithmetic: a second workgroup per
+//     CU hides one's barrier and softmax under the other's MFMAs, and the QI = 4 instantiation (80 accumulator + 48 Q-fragment
+//     registers per lane before any score) has no room for 8 more score registers under a 256-register cap: as it is, the compiler
+//     reports 164 VGPRs for QI = 1 and 256 VGPRs plus 14 spilled (60 B of scratch per lane) for QI = 4.  Neither chunk size has been
+//     timed against the other.
+//   * A chunk is 96 * 10 = 960 16-byte pieces of K and 80 * 12 = 960 of V^T: thread tid moves pieces tid + 256 i, i < 4, of each (the
+//     last 64 indices are past the chunk and skipped).  Double buffering, the one barrier per chunk, the partial last chunk (32 or 64
+//     keys, skipped by workgroup-uniform tests) and the online softmax with its all--inf conventions are attn64_stream_kernel's
+//     (header above), with 5 output tiles and the 32 + 32 + 16 channel split of attn80_kernel: lane groups 2, 3 of the third MFMA
+//     hold zeros and load nothing.
+//   * QI tiles keep separate states and run one tile's instructions in one tile's order; multiply-adds that could contract
+//     differently are fmaf.  No atomics, fixed order: bitwise repeatable, independent of B and QI.
+// tests/test_siglip_cpu.py restates the LDS addresses against the bank model; tests/test_siglip_attention_gpu.py holds the parity.
+constexpr int TAS80_CK = 96;                         // keys per chunk
+constexpr int TAS80_VP = 64 * (TAS80_CK / 32);       // V^T row pitch of a chunk, bytes (m = 3: odd)
+constexpr int TAS80_KB = TAS80_CK * 160;             // K image of a chunk, bytes
+constexpr int TAS80_BUF = TAS80_KB + 80 * TAS80_VP;  // one buffer
+constexpr int TAS80_LDS = 2 * TAS80_BUF;
+constexpr int TAS80_NP = TAS80_CK * 10;              // 16-byte pieces of a chunk's K; as many of its V^T
+static_assert(TAS80_CK % 32 == 0 && (TAS80_CK / 32) % 2 == 1 && TAS80_NP == 80 * (TAS80_CK / 8) && TAS80_NP <= 4 * 256, "a thread stages <= 4 + 4 pieces");
+static_assert(TAS80_BUF % 256 == 0 && TAS80_KB % 256 == 0 && 2 * TAS80_LDS <= 160 * 1024, "bank-aligned images, two workgroups per CU");
+
+// chunk's K rows and V^T columns -> registers; nk: its keys (0: nothing to load)
+__device__ __forceinline__ void tas80_fetch(u32x4 (&kr)[4], u32x4 (&vr)[4], const bf16_t* __restrict__ k, int64_t ldk, const bf16_t* __restrict__ vt,
+                                            int64_t ldvt, int head, int key0, int nk, int tid) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int idx = tid + i * 256;
+    const int r = idx / 10, c = idx - r * 10;
+    if (idx < nk * 10) kr[i] = *(const u32x4*)(k + (int64_t)(key0 + r) * ldk + head * 80 + c * 8);
+    const int d = idx / (TAS80_CK / 8), m = idx - d * (TAS80_CK / 8);
+    if (idx < TAS80_NP && m * 8 < nk) vr[i] = *(const u32x4*)(vt + (int64_t)(head * 80 + d) * ldvt + key0 + m * 8);
+  }
+}
+
+// registers -> one LDS buffer, in attn80_kernel's images
+__device__ __forceinline__ void tas80_stash(const u32x4 (&kr)[4], const u32x4 (&vr)[4], char* buf, int nk, int tid) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int idx = tid + i * 256;
+    if (idx < nk * 10) *(u32x4*)(buf + idx * 16) = kr[i];
+    const int d = idx / (TAS80_CK / 8), m = idx - d * (TAS80_CK / 8);
+    if (idx < TAS80_NP && m * 8 < nk) {
+      const int blk = (m * 8) >> 5, kap = (m * 8) & 31;
+      const int tile = kap >> 4, g0 = (kap & 15) >> 2;
+      const int sw = (0x78 >> (2 * ((d & 15) >> 2))) & 3;
+      char* dst = buf + TAS80_KB + d * TAS80_VP + blk * 64 + 8 * tile;
+      u32x2 lo, hi;
+      lo[0] = vr[i][0]; lo[1] = vr[i][1]; hi[0] = vr[i][2]; hi[1] = vr[i][3];
+      *(u32x2*)(dst + ((g0 ^ sw) << 4)) = lo;
+      *(u32x2*)(dst + (((g0 + 1) ^ sw) << 4)) = hi;
+    }
+  }
+}
+
+template <int QI>   // query tiles per wave, as attn80_kernel
+__global__ __launch_bounds__(256, 2) void attn80_stream_kernel(const bf16_t* __restrict__ q, int64_t ldq, const bf16_t* __restrict__ k, int64_t ldk,
+                                                               const bf16_t* __restrict__ vt, int64_t ldvt, const float* __restrict__ bias,
+                                                               int64_t bias_hs, bf16_t* __restrict__ out, int64_t ldo, int S, int S_pad, float scale) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int l15 = lane & 15, g = lane >> 4;
+  const int head = blockIdx.y, qb = blockIdx.x;
+  {
+    const int64_t r0 = (int64_t)blockIdx.z * S_pad;
+    q += r0 * ldq; k += r0 * ldk; vt += r0; out += r0 * ldo;
+  }
+  const float NINF = -__builtin_huge_valf();
+  const float LOG2E = 1.4426950408889634f;
+  const float sl2 = scale * LOG2E;
+  const int vsw = (0x78 >> (2 * (l15 >> 2))) & 3;   // every V^T fragment row is 16 dt + l15
+  const bf16x8 zero8 = __builtin_bit_cast(bf16x8, u32x4{0u, 0u, 0u, 0u});
+  // ---- per query tile: Q fragments, bias row, softmax state -----------------------------------------------------------------------
+  bf16x8 qf[QI][3];
+  const float* const bbase = bias ? bias + head * bias_hs : nullptr;   // uniform; a lane keeps a 32-bit offset per query tile
+  int boff[QI];
+  float mrun[QI], lrun[QI];
+  f32x4 oacc[QI][5];
+#pragma unroll
+  for (int it = 0; it < QI; ++it) {
+    const int q_row = (qb * QI + it) * 64 + w * 16 + l15;
+    const int q_ld = q_row < S_pad ? q_row : S_pad - 1;
+#pragma unroll
+    for (int ds = 0; ds < 2; ++ds) qf[it][ds] = *(const bf16x8*)(q + (int64_t)q_ld * ldq + head * 80 + ds * 32 + g * 8);
+    qf[it][2] = zero8;
+    if (g < 2) qf[it][2] = *(const bf16x8*)(q + (int64_t)q_ld * ldq + head * 80 + 64 + g * 8);
+    boff[it] = q_ld * S_pad + 4 * g;   // < 2048^2
+    mrun[it] = NINF;
+    lrun[it] = 0.f;
+#pragma unroll
+    for (int dt = 0; dt < 5; ++dt) oacc[it][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  // ---- chunk 0 -> buffer 0 -----------------------------------------------------------------------------------------------------------
+  const int nch = (S_pad + TAS80_CK - 1) / TAS80_CK;
+  u32x4 kr[4], vr[4];
+  tas80_fetch(kr, vr, k, ldk, vt, ldvt, head, 0, min(TAS80_CK, S_pad), tid);
+  tas80_stash(kr, vr, smem, min(TAS80_CK, S_pad), tid);
+  __syncthreads();
+#pragma unroll 1
+  for (int c = 0; c < nch; ++c) {
+    const int key0 = c * TAS80_CK, nk = min(TAS80_CK, S_pad - key0);
+    const int nk_next = c + 1 < nch ? min(TAS80_CK, S_pad - key0 - TAS80_CK) : 0;
+    tas80_fetch(kr, vr, k, ldk, vt, ldvt, head, key0 + TAS80_CK, nk_next, tid);   // in flight under this chunk's MFMAs
+    const char* const kl = smem + (c & 1) * TAS80_BUF;
+    const char* const vl = kl + TAS80_KB;
+    const int nt = nk >> 4;
+#pragma unroll
+    for (int it = 0; it < QI; ++it) {
+      if ((qb * QI + it) * 64 < S_pad) {
+        // scores: S^T tile t = K[key0 + 16t ..] Q^T: this lane holds keys key0 + 16t + 4g + r of query l15
+        f32x4 s[TAS80_CK / 16];
+        float cm = NINF;
+#pragma unroll
+        for (int t = 0; t < TAS80_CK / 16; ++t) {
+          if (t < nt) {
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            const int r = t * 16 + l15;
+#pragma unroll
+            for (int ds = 0; ds < 2; ++ds) {
+              const bf16x8 kf = *(const bf16x8*)(kl + r * 160 + ((ds * 4 + g) << 4));
+              acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[it][ds], acc, 0, 0, 0);
+            }
+            bf16x8 kf2 = zero8;
+            if (g < 2) kf2 = *(const bf16x8*)(kl + r * 160 + ((8 + g) << 4));
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf2, qf[it][2], acc, 0, 0, 0);
+            f32x4 b = {0.f, 0.f, 0.f, 0.f};
+            if (bbase) b = *(const f32x4*)(bbase + (boff[it] + key0 + t * 16));
+#pragma unroll
+            for (int r2 = 0; r2 < 4; ++r2) {
+              acc[r2] = __builtin_fmaf(acc[r2], sl2, b[r2] * LOG2E);
+              cm = fmaxf(cm, acc[r2]);
+            }
+            s[t] = acc;
+          }
+        }
+        cm = fmaxf(cm, __shfl_xor(cm, 16));
+        cm = fmaxf(cm, __shfl_xor(cm, 32));
+        const float mnew = fmaxf(mrun[it], cm);
+        const float msub = mnew > NINF ? mnew : 0.f;               // only -inf so far: keep the arithmetic finite
+        const float alpha = __builtin_amdgcn_exp2f(mrun[it] - msub);   // -inf - finite: 0; m unchanged: exp2(0) = 1
+        mrun[it] = mnew;
+#pragma unroll
+        for (int dt = 0; dt < 5; ++dt)
+#pragma unroll
+          for (int r2 = 0; r2 < 4; ++r2) oacc[it][dt][r2] *= alpha;
+        float ls = 0.f;
+#pragma unroll
+        for (int b = 0; b < TAS80_CK / 32; ++b) {
+          if (2 * b < nt) {
+            float p[8];
+#pragma unroll
+            for (int r2 = 0; r2 < 4; ++r2) {
+              p[r2] = __builtin_amdgcn_exp2f(s[2 * b][r2] - msub);
+              p[4 + r2] = __builtin_amdgcn_exp2f(s[2 * b + 1][r2] - msub);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) ls += p[i];
+            const bf16x8 pf = __builtin_bit_cast(bf16x8, pack8(p));
+#pragma unroll
+            for (int dt = 0; dt < 5; ++dt) {
+              const bf16x8 vf = *(const bf16x8*)(vl + (dt * 16 + l15) * TAS80_VP + b * 64 + ((g ^ vsw) << 4));
+              oacc[it][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, oacc[it][dt], 0, 0, 0);
+            }
+          }
+        }
+        lrun[it] = __builtin_fmaf(lrun[it], alpha, ls);
+      }
+    }
+    tas80_stash(kr, vr, smem + ((c + 1) & 1) * TAS80_BUF, nk_next, tid);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int it = 0; it < QI; ++it) {
+    const int q_row = (qb * QI + it) * 64 + w * 16 + l15;
+    float l = lrun[it];
+    l += __shfl_xor(l, 16);
+    l += __shfl_xor(l, 32);
+    if (q_row < S) {
+      const float inv = 1.0f / l;
+      bf16_t* orow = out + (int64_t)q_row * ldo + head * 80 + 4 * g;
+#pragma unroll
+      for (int dt = 0; dt < 5; ++dt) {
+        u32x2 v;
+        v[0] = pack2(oacc[it][dt][0] * inv, oacc[it][dt][1] * inv);
+        v[1] = pack2(oacc[it][dt][2] * inv, oacc[it][dt][3] * inv);
+        *(u32x2*)(orow + dt * 16) = v;
+      }
+    }
+  }
+}
+
 // ---- host side (TextCtx / TextSizes: text_internal.hpp) ------------------------------------------------------------------------
 int text_ctx(TextCtx& c, const TextSizes& z, int B, int S, int S_pad, const rf_workspace* ws, hipStream_t st, const char* who) {
   RF_REQUIRE(ws && ws->base && aligned16(ws->base) && ws->bytes >= z.total, RF_ERR_WORKSPACE, "%s: workspace %lld < required %lld bytes", who,
@@ -625,6 +835,16 @@ int text_gemm(TextCtx& c, const bf16_t* x, int64_t ldx, const void* w, const voi
     if (t256 >= 16 && t256 < 200 && K / 64 >= 16) d.schedule = RF_SCHED_STREAMK;
   }
   return rf_gemm_bf16(&d, c.st);
+}
+
+// token (+ position) embedding rows into the residual stream c.X
+int text_embed_rows(TextCtx& c, const void* table, const void* pos, const int32_t* ids, int D, int vocab) {
+  const int R = c.B * c.S_pad;
+  ProfScope prof(RF_KC_ROWOP, (double)R * D * 6, c.st);
+  hipLaunchKernelGGL(embed_rows_kernel, dim3(grid_for((int64_t)R * D / 8)), dim3(256), 0, c.st, (const bf16_t*)table, (const bf16_t*)pos, ids, c.X, c.S, c.S_pad,
+                     R, D, vocab);
+  RF_LAUNCH_CHECK();
+  return RF_OK;
 }
 
 int text_attn_max_keys(int head_dim) { return head_dim == 64 ? TA_MAXS : head_dim == 80 ? TA80_MAXS : 0; }   // 0: no kernel for that head dim
@@ -674,6 +894,32 @@ static int text_attention_launch(int head_dim, int qi, int stream_keys, const bf
   return RF_OK;
 }
 
+// The head-dim-80 route with streamed keys, beside the launch site above and taken by rf_text_attention80 and by clip_layers' route80
+// (the SigLIP towers) alone (the CLIP entry points,
+// rf_text_attention and rf_debug_text_attention keep their refusals at head dim 80): stream_keys = 0 launches attn80_kernel up to
+// TA80_MAXS keys -- through text_attention_launch, i.e. the very launch the CLIP towers make -- and attn80_stream_kernel beyond;
+// stream_keys = 1 launches attn80_stream_kernel at any S_pad.  qi and the grid as above.
+static int text_attention80_launch(int qi, int stream_keys, const bf16_t* q, int64_t ldq, const bf16_t* k, int64_t ldk, const bf16_t* vt, int64_t ldvt,
+                                   const float* bias, int64_t bias_hs, bf16_t* out, int64_t ldo, int heads, int B, int S, int S_pad, float scale,
+                                   hipStream_t st) {
+  if (!stream_keys && S_pad <= TA80_MAXS)
+    return text_attention_launch(80, qi, 0, q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, heads, B, S, S_pad, scale, st);
+  RF_REQUIRE(S_pad <= TAS80_MAXS, RF_ERR_SHAPE, "head-dim-80 attention: S_pad=%d > %d keys, the limit of the streaming-keys kernel", S_pad, TAS80_MAXS);
+  const bool wide = qi ? qi == 4 : (int64_t)heads * B * cdiv(S_pad, 256) >= 256;
+  const dim3 grid(cdiv(S_pad, wide ? 256 : 64), heads, B);
+  static bool sattr = false;
+  if (!sattr) {
+    RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn80_stream_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, TAS80_LDS));
+    RF_CHECK_HIP(hipFuncSetAttribute((const void*)attn80_stream_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, TAS80_LDS));
+    sattr = true;
+  }
+  ProfScope prof(RF_KC_ATTN, 4.0 * (double)S_pad * S_pad * 80.0 * heads * B, st);
+  auto* const skern = wide ? attn80_stream_kernel<4> : attn80_stream_kernel<1>;
+  hipLaunchKernelGGL(skern, grid, dim3(256), TAS80_LDS, st, q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, S, S_pad, scale);
+  RF_LAUNCH_CHECK();
+  return RF_OK;
+}
+
 // q | k [R][2 * inner], V^T [inner][R], out [R][ld_ao] (ld_ao = inner, or inner rounded up to the GEMM's K-tile, see clip_layers)
 int text_attention(TextCtx& c, int head_dim, int heads, int inner, int64_t ld_ao, const float* bias, int64_t bias_hs, float scale) {
   return text_attention_launch(head_dim, 0, 0, c.QK, (int64_t)2 * inner, c.QK + inner, (int64_t)2 * inner, c.VT, (int64_t)c.B * c.S_pad, bias, bias_hs, c.AO,
@@ -681,9 +927,10 @@ int text_attention(TextCtx& c, int head_dim, int heads, int inner, int64_t ld_ao
 }
 
 // A CLIP tower's activation over x[0 .. n) in place, n % 8 == 0
-static int clip_act_inplace(int act, bf16_t* x, int64_t n, hipStream_t st) {
+int clip_act_inplace(int act, bf16_t* x, int64_t n, hipStream_t st) {
   ProfScope prof(RF_KC_ROWOP, (double)n * 4, st);
-  auto* const kern = act == RF_CLIP_ACT_GELU ? clip_act_kernel<RF_CLIP_ACT_GELU> : clip_act_kernel<RF_CLIP_ACT_QUICK_GELU>;
+  auto* const kern = act == RF_CLIP_ACT_GELU ? clip_act_kernel<RF_CLIP_ACT_GELU>
+                     : act == RF_CLIP_ACT_GELU_TANH ? clip_act_kernel<RF_CLIP_ACT_GELU_TANH> : clip_act_kernel<RF_CLIP_ACT_QUICK_GELU>;
   hipLaunchKernelGGL(kern, dim3(grid_for(n / 8)), dim3(256), 0, st, x, n / 8);
   RF_LAUNCH_CHECK();
   return RF_OK;
@@ -694,9 +941,13 @@ static int clip_act_inplace(int act, bf16_t* x, int64_t n, hipStream_t st) {
 // o: head dim (64 | 80) and activation (validated by clip_opts_check).  Dp = D rounded up to the GEMM's 64-element K-tile: the
 // operands whose K axis is the hidden width (Xn, AO; the weights, packed by the binding) have row pitch Dp and zeros in columns
 // D .. Dp - 1.  Dp == D for every hidden width that is a multiple of 64 (all head-dim-64 towers, ViT-H's 1280): nothing moves there.
+// inner: the attention width heads * head_dim where it differs from D (the SigLIP towers: heads of d <= 80 channels zero-padded to 80 by
+// the binding, so q | k is [R][2 inner], V^T [inner][R], w_o [D][Ip] with Ip = inner rounded up to the K-tile); 0 = D, the CLIP towers,
+// for which every launch below is what it was.  route80: the attention goes through text_attention80_launch (head dim 80, keys
+// streamed beyond 480) instead of text_attention; mask may then be NULL when S == S_pad.
 int clip_layers(TextCtx& c, const rf_clip_layer* layer, int layers, int heads, int D, int F, const float* mask, float eps, const char* who,
-                const rf_clip_tower_opts& o) {
-  const int R = c.B * c.S_pad, Dp = (int)round_up(D, 64);
+                const rf_clip_tower_opts& o, int inner, bool route80) {
+  const int R = c.B * c.S_pad, Dp = (int)round_up(D, 64), I = inner ? inner : D, Ip = (int)round_up(I, 64);
   hipStream_t st = c.st;
   if (Dp != D) RF_CHECK_HIP(hipMemsetAsync(c.Xn, 0, (size_t)R * Dp * 2, st));   // the pad columns of Xn: LayerNorm writes D columns per row
   for (int i = 0; i < layers; ++i) {
@@ -704,10 +955,13 @@ int clip_layers(TextCtx& c, const rf_clip_layer* layer, int layers, int heads, i
     RF_REQUIRE(L.ln1_scale && L.ln1_shift && L.w_qk && L.b_qk && L.w_v && L.w_o && L.b_o && L.ln2_scale && L.ln2_shift && L.w_fc1 && L.b_fc1 && L.w_fc2 &&
                    L.b_fc2, RF_ERR_NULL, "%s: layer %d has NULL weights", who, i);
     RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, Dp, R, D, L.ln1_scale, L.ln1_shift, eps, st));
-    RF_TRY(text_gemm(c, c.Xn, Dp, L.w_qk, L.b_qk, R, 2 * D, Dp, c.QK, 2 * D, RF_EPI_STORE, nullptr));
-    RF_TRY(text_gemm(c, (const bf16_t*)L.w_v, Dp, c.Xn, nullptr, D, R, Dp, c.VT, R, RF_EPI_STORE, nullptr));
-    RF_TRY(text_attention(c, o.head_dim, heads, D, Dp, mask, 0, 1.0f));
-    RF_TRY(text_gemm(c, c.AO, Dp, L.w_o, L.b_o, R, D, Dp, c.X, D, RF_EPI_STORE, c.X));
+    RF_TRY(text_gemm(c, c.Xn, Dp, L.w_qk, L.b_qk, R, 2 * I, Dp, c.QK, 2 * I, RF_EPI_STORE, nullptr));
+    RF_TRY(text_gemm(c, (const bf16_t*)L.w_v, Dp, c.Xn, nullptr, I, R, Dp, c.VT, R, RF_EPI_STORE, nullptr));
+    if (route80)
+      RF_TRY(text_attention80_launch(0, 0, c.QK, (int64_t)2 * I, c.QK + I, (int64_t)2 * I, c.VT, (int64_t)R, mask, 0, c.AO, Ip, heads, c.B, c.S, c.S_pad, 1.0f, st));
+    else
+      RF_TRY(text_attention(c, o.head_dim, heads, I, Ip, mask, 0, 1.0f));
+    RF_TRY(text_gemm(c, c.AO, Ip, L.w_o, L.b_o, R, D, Ip, c.X, D, RF_EPI_STORE, c.X));
     RF_TRY(rf_layernorm_modulate(c.X, D, c.Xn, Dp, R, D, L.ln2_scale, L.ln2_shift, eps, st));
     RF_TRY(text_gemm(c, c.Xn, Dp, L.w_fc1, L.b_fc1, R, F, Dp, c.HID, F, RF_EPI_STORE, nullptr));
     RF_TRY(clip_act_inplace(o.act, c.HID, (int64_t)R * F, st));
@@ -934,4 +1188,20 @@ extern "C" int rf_text_attention(int32_t head_dim, int32_t qi, int32_t stream_ke
   RF_TRY(text_attention_args_check(who, head_dim, text_attn_stream_max_keys(head_dim), q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, heads, B, S, S_pad));
   return text_attention_launch(head_dim, qi, stream_keys, (const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)vt, ldvt, bias, bias_hs, (bf16_t*)out, ldo,
                                heads, B, S, S_pad, scale, (hipStream_t)stream);
+}
+
+// rf_text_attention's contract at head dim 80 (a tower whose heads are 80 channels wide, or narrower ones zero-padded to 80 by the
+// binding: SigLIP so400m's 72), through text_attention80_launch: resident keys up to 480 (attn80_kernel, the CLIP-H towers' launch),
+// streamed keys up to 2048 (attn80_stream_kernel).  stream_keys = 1 runs the streaming kernel at any S_pad.  A symbol of its own, so
+// rf_text_attention and the CLIP entry points answer head dim 80 as they always did.  Everything is validated before the first HIP call.
+extern "C" int rf_text_attention80(int32_t qi, int32_t stream_keys, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vt, int64_t ldvt,
+                                   const float* bias, int64_t bias_hs, void* out, int64_t ldo, int32_t heads, int32_t B, int32_t S, int32_t S_pad, float scale,
+                                   void* stream) {
+  const char* who = "rf_text_attention80";
+  RF_REQUIRE(qi == 0 || qi == 1 || qi == 4, RF_ERR_UNSUPPORTED, "%s: qi=%d (instantiations exist for 1 and 4; 0 = the product's rule)", who, qi);
+  RF_REQUIRE(stream_keys == 0 || stream_keys == 1, RF_ERR_UNSUPPORTED, "%s: stream_keys=%d (0 = resident up to %d keys and streamed beyond, 1 = streamed)", who,
+             stream_keys, TA80_MAXS);
+  RF_TRY(text_attention_args_check(who, 80, TAS80_MAXS, q, ldq, k, ldk, vt, ldvt, bias, bias_hs, out, ldo, heads, B, S, S_pad));
+  return text_attention80_launch(qi, stream_keys, (const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)vt, ldvt, bias, bias_hs, (bf16_t*)out, ldo, heads,
+                                 B, S, S_pad, scale, (hipStream_t)stream);
 }

@@ -17,6 +17,7 @@ namespace rf {
 constexpr int TA_MAXS = 512;     // keys of attn64_kernel
 constexpr int TA80_MAXS = 480;   // keys of attn80_kernel (text.hip: K + V^T of a head at head dim 80 within the 160 KiB LDS)
 constexpr int TAS_MAXS = 2048;   // keys of attn64_stream_kernel (head dim 64 beyond TA_MAXS): 448 px / 14 needs 1056; a shared fp32 mask of 2048^2 is 16 MiB
+constexpr int TAS80_MAXS = 2048;   // keys of attn80_stream_kernel (head dim 80 beyond TA80_MAXS, rf_text_attention80): as at head dim 64
 constexpr rf_clip_tower_opts CLIP_L_OPTS = {64, RF_CLIP_ACT_QUICK_GELU};   // the towers of clip-vit-large-patch14: the entry points without opts
 
 struct TextCtx {
@@ -49,7 +50,9 @@ int text_attn_max_keys(int head_dim);          // the resident kernels: TA_MAXS 
 int text_attn_stream_max_keys(int head_dim);   // the streaming-keys kernel: TAS_MAXS at head dim 64, 0 elsewhere
 int text_attention(TextCtx& c, int head_dim, int heads, int inner, int64_t ld_ao, const float* bias, int64_t bias_hs, float scale);
 int clip_layers(TextCtx& c, const rf_clip_layer* layer, int layers, int heads, int D, int F, const float* mask, float eps, const char* who,
-                const rf_clip_tower_opts& o);
+                const rf_clip_tower_opts& o, int inner = 0, bool route80 = false);   // inner / route80: the SigLIP towers (siglip.hip)
+int clip_act_inplace(int act, bf16_t* x, int64_t n, hipStream_t st);   // rf_clip_act | RF_CLIP_ACT_GELU_TANH over x[0 .. n) in place, n % 8 == 0
+int text_embed_rows(TextCtx& c, const void* table, const void* pos, const int32_t* ids, int D, int vocab);
 int clip_opts_check(const rf_clip_tower_opts* o, int hidden, int heads, int S_pad, const char* who);
 
 }  // namespace rf

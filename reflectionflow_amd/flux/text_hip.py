@@ -412,3 +412,271 @@ class HipTextEncoders:
 
     def __call__(self, prompt, max_sequence_length: int, dtype, device):
         return self.encode_t5(prompt, max_sequence_length, dtype, device), self.encode_clip(prompt, dtype, device)
+
+
+# ---- SigLIP towers (csrc/siglip.hip): transformers' SiglipModel state dict -> rf_siglip_vision_weights / rf_siglip_text_weights --------
+SIGLIP_HEAD = 80           # the attention kernels' head dim: every head of d <= 80 channels is zero-padded to it, which is exact
+
+
+def _pad_rows_per_head(w: torch.Tensor, heads: int, d: int) -> torch.Tensor:
+    """[heads * d, ...] -> [heads * 80, ...]: rows 80 h + d .. 80 h + 79 of every head zero"""
+    tail = w.shape[1:]
+    out = torch.zeros(heads, SIGLIP_HEAD, *tail, dtype=w.dtype)
+    out[:, :d] = w.reshape(heads, d, *tail)
+    return out.reshape(heads * SIGLIP_HEAD, *tail)
+
+
+def _pad_rows(w: torch.Tensor, n: int) -> torch.Tensor:
+    return w if w.shape[0] == n else torch.cat([w, torch.zeros(n - w.shape[0], *w.shape[1:], dtype=w.dtype)], 0)
+
+
+def siglip_head_dim(who: str, hidden: int, heads: int) -> int:
+    d = hidden // max(heads, 1)
+    if heads <= 0 or d * heads != hidden:
+        raise RFError(f"{who}: hidden {hidden} is not a multiple of {heads} heads")
+    if d > SIGLIP_HEAD:
+        raise RFError(f"{who}: head dim {d} > {SIGLIP_HEAD}: the attention kernels serve head dims up to {SIGLIP_HEAD} (zero-padded)")
+    if d % 8:
+        raise RFError(f"{who}: head dim {d} is not a multiple of 8")
+    return d
+
+
+def siglip_pack_mlp(fc1_w, fc1_b, fc2_w, fc2_b) -> Dict[str, torch.Tensor]:
+    """intermediate_size padded to a multiple of 64 with zero fc1 rows / biases and zero fc2 columns: gelu(0) = 0 keeps it exact"""
+    f = lambda t: t.detach().float().cpu()  # noqa: E731
+    F = fc1_w.shape[0]
+    Fp = (F + 63) // 64 * 64
+    return dict(w_fc1=_pad_rows(f(fc1_w), Fp), b_fc1=_pad_rows(f(fc1_b), Fp), w_fc2=_pad_rows(f(fc2_w).t().contiguous(), Fp).t().contiguous(),
+                b_fc2=f(fc2_b))
+
+
+def siglip_pack_layers(sd: Dict[str, torch.Tensor], n_layers: int, heads: int) -> List[Dict[str, torch.Tensor]]:
+    """The encoder layers of a SigLIP tower (`encoder.layers.N.*` keys, prefix stripped) as fp32 CPU tensors in the packed form
+    include/rf_flux.h documents: heads padded d -> 80 (zero q / k / v rows and biases, zero out_proj columns), 1/sqrt(d) of the true d
+    folded into q, v bias folded into the out-projection bias, intermediate size padded to a multiple of 64.  Pure repacking: the
+    layer computes what the unpacked one does up to fp32 round-off (tests/test_siglip_cpu.py)."""
+    f = lambda t: t.detach().float().cpu()  # noqa: E731
+    out = []
+    for i in range(n_layers):
+        p = f"encoder.layers.{i}."
+        D = sd[p + "self_attn.q_proj.weight"].shape[1]
+        d = siglip_head_dim("siglip_pack_layers", D, heads)
+        qs = d ** -0.5
+        wq, bq = f(sd[p + "self_attn.q_proj.weight"]) * qs, f(sd[p + "self_attn.q_proj.bias"]) * qs
+        wk, bk = f(sd[p + "self_attn.k_proj.weight"]), f(sd[p + "self_attn.k_proj.bias"])
+        wv, bv = f(sd[p + "self_attn.v_proj.weight"]), f(sd[p + "self_attn.v_proj.bias"])
+        wo, bo = f(sd[p + "self_attn.out_proj.weight"]), f(sd[p + "self_attn.out_proj.bias"])
+        y = dict(ln1_w=f(sd[p + "layer_norm1.weight"]), ln1_b=f(sd[p + "layer_norm1.bias"]),
+                 ln2_w=f(sd[p + "layer_norm2.weight"]), ln2_b=f(sd[p + "layer_norm2.bias"]),
+                 w_qk=torch.cat([_pad_rows_per_head(wq, heads, d), _pad_rows_per_head(wk, heads, d)], 0),
+                 b_qk=torch.cat([_pad_rows_per_head(bq, heads, d), _pad_rows_per_head(bk, heads, d)], 0),
+                 w_v=_pad_rows_per_head(wv, heads, d),
+                 w_o=_pad_rows_per_head(wo.t().contiguous(), heads, d).t().contiguous(),
+                 b_o=bo + wo @ bv)
+        y.update(siglip_pack_mlp(sd[p + "mlp.fc1.weight"], sd[p + "mlp.fc1.bias"], sd[p + "mlp.fc2.weight"], sd[p + "mlp.fc2.bias"]))
+        out.append(y)
+    return out
+
+
+def siglip_pack_pool_head(sd: Dict[str, torch.Tensor], heads: int) -> Dict[str, torch.Tensor]:
+    """SiglipMultiheadAttentionPoolingHead (`head.*` keys): K | V projection, the probe's query (input-independent: computed here once,
+    1/sqrt(d) folded in), out_proj, layernorm, the padded MLP"""
+    f = lambda t: t.detach().float().cpu()  # noqa: E731
+    wi, bi = f(sd["head.attention.in_proj_weight"]), f(sd["head.attention.in_proj_bias"])
+    D = wi.shape[1]
+    d = siglip_head_dim("siglip_pack_pool_head", D, heads)
+    probe = f(sd["head.probe"]).reshape(D)
+    y = dict(probe_q=(wi[:D] @ probe + bi[:D]) * d ** -0.5, w_kv=wi[D:].contiguous(), b_kv=bi[D:].contiguous(),
+             w_po=f(sd["head.attention.out_proj.weight"]), b_po=f(sd["head.attention.out_proj.bias"]),
+             hln_w=f(sd["head.layernorm.weight"]), hln_b=f(sd["head.layernorm.bias"]))
+    y.update(siglip_pack_mlp(sd["head.mlp.fc1.weight"], sd["head.mlp.fc1.bias"], sd["head.mlp.fc2.weight"], sd["head.mlp.fc2.bias"]))
+    return y
+
+
+def _siglip_layer_structs(k: "_Keep", packed: List[Dict[str, torch.Tensor]]) -> "C.Array":
+    layers = (L.rf_clip_layer * len(packed))()
+    for y, p in zip(layers, packed):
+        y.ln1_scale, y.ln1_shift = k.t(p["ln1_w"] - 1.0), k.t(p["ln1_b"])
+        y.ln2_scale, y.ln2_shift = k.t(p["ln2_w"] - 1.0), k.t(p["ln2_b"])
+        y.w_qk, y.b_qk, y.w_v = k.t(_kpad(p["w_qk"])), k.t(p["b_qk"]), k.t(_kpad(p["w_v"]))
+        y.w_o, y.b_o = k.t(_kpad(p["w_o"])), k.t(p["b_o"])
+        y.w_fc1, y.b_fc1, y.w_fc2, y.b_fc2 = k.t(_kpad(p["w_fc1"])), k.t(p["b_fc1"]), k.t(p["w_fc2"]), k.t(p["b_fc2"])
+    return layers
+
+
+def _count_layers(sd, who):
+    n = 0
+    while f"encoder.layers.{n}.layer_norm1.weight" in sd:
+        n += 1
+    if n == 0:
+        raise RFError(f"{who}: no encoder.layers.* keys in the state dict")
+    return n
+
+
+class HipSiglipVisionEncoder:
+    """SiglipVisionModel of a Hugging Face `SiglipModel` state dict (`vision_model.*`; the prefix may be absent): images ->
+    pooler_output [B, hidden] bf16 (rf_siglip_preprocess + rf_siglip_vision_encode).  The interface of HipClipVisionEncoder."""
+
+    MAX_BATCH = 64
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], num_heads: int, device, eps: float = 1e-6, image_size: Optional[int] = None):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RFError(f"HipSiglipVisionEncoder: device {device}; the HIP path has no CPU fallback")
+        L.load()
+        sd = {(k[len("vision_model."):] if k.startswith("vision_model.") else k): v for k, v in state_dict.items()}
+        n_layers = _count_layers(sd, "HipSiglipVisionEncoder")
+        pw = sd["embeddings.patch_embedding.weight"]                     # [hidden, 3, p, p]
+        D, _, P, _ = pw.shape
+        d = siglip_head_dim("HipSiglipVisionEncoder", D, num_heads)
+        T = sd["embeddings.position_embedding.weight"].shape[0]
+        g = int(round(math.sqrt(T)))
+        if g * g != T:
+            raise RFError(f"HipSiglipVisionEncoder: {T} positions is not a square grid")
+        if image_size is not None and int(image_size) // P != g:
+            raise RFError(f"HipSiglipVisionEncoder: image_size {image_size} with patch {P} needs {(int(image_size) // P) ** 2} position rows, "
+                          f"the state dict has {T} (a {g * P}-pixel tower)")
+        # the patch convolution is "valid": so400m/14 at 384 px has 27 x 27 patches over 378 of its 384 pixels
+        self.device, self.heads, self.hidden, self.patch, self.image_size = device, num_heads, D, P, int(image_size) if image_size is not None else g * P
+        self.tokens, self.s_pad, self.k_pad, self.proj_dim = T, _pad32(T), (3 * P * P + 63) // 64 * 64, D
+        k = self._k = _Keep(device)
+        f = lambda t: t.detach().float()  # noqa: E731
+        packed = siglip_pack_layers(sd, n_layers, num_heads)
+        self._layers = _siglip_layer_structs(k, packed)
+        hp = siglip_pack_pool_head(sd, num_heads)
+        wpad = torch.zeros(D, self.k_pad)
+        wpad[:, : 3 * P * P] = f(pw).reshape(D, 3 * P * P).cpu()
+        w = self._w = L.rf_siglip_vision_weights()
+        w.layers, w.hidden, w.heads, w.head_dim, w.inter = n_layers, D, num_heads, d, packed[0]["w_fc1"].shape[0]
+        w.image_size, w.patch, w.mask_S, w.eps = self.image_size, P, self.s_pad, eps
+        w.patch_w, w.patch_b = k.t(wpad), k.t(sd["embeddings.patch_embedding.bias"])
+        w.pos_embed = k.t(sd["embeddings.position_embedding.weight"])
+        w.post_ln_scale, w.post_ln_shift = k.t(f(sd["post_layernorm.weight"]) - 1.0), k.t(sd["post_layernorm.bias"])
+        self._mask = None
+        if self.s_pad != T:
+            mask = torch.zeros(self.s_pad, self.s_pad, device=device)
+            mask[:, T:] = float("-inf")
+            self._mask = mask.contiguous()
+            w.mask = self._mask.data_ptr()
+        w.layer = C.cast(self._layers, C.POINTER(L.rf_clip_layer))
+        if hp["w_fc1"].shape[0] != w.inter:
+            raise RFError("HipSiglipVisionEncoder: the pooling head's MLP and the layers' MLP differ in width")
+        w.w_kv, w.b_kv, w.probe_q = k.t(_kpad(hp["w_kv"])), k.t(hp["b_kv"]), k.t(hp["probe_q"], torch.float32)
+        w.w_po, w.b_po = k.t(_kpad(hp["w_po"])), k.t(hp["b_po"])
+        w.hln_scale, w.hln_shift = k.t(hp["hln_w"] - 1.0), k.t(hp["hln_b"])
+        w.w_hfc1, w.b_hfc1, w.w_hfc2, w.b_hfc2 = k.t(_kpad(hp["w_fc1"])), k.t(hp["b_fc1"]), k.t(hp["w_fc2"]), k.t(hp["b_fc2"])
+        self._ws = _Workspace(device)
+
+    def alloc_patches(self, n: int) -> torch.Tensor:
+        return torch.empty(n, self.tokens, self.k_pad, dtype=BF, device=self.device)
+
+    def preprocess(self, img: torch.Tensor, strides: Tuple[int, int, int, int], a: float, b: float, out: torch.Tensor, H: int, W: int,
+                   n: int = 1) -> torch.Tensor:
+        """rf_siglip_preprocess of n images read through element strides (image, row, pixel, channel): level = rint(255 clamp(a v + b,
+        0, 1)), then SiglipImageProcessor's resize of both axes to image_size and (v / 255 - 0.5) / 0.5."""
+        if not (img.is_cuda and out.is_cuda) or img.dtype != BF:
+            raise RFError("HipSiglipVisionEncoder.preprocess: needs bf16 tensors on the device")
+        si, sr, sp, sc = (int(s) for s in strides)
+        L.check(L.load().rf_siglip_preprocess(img.data_ptr(), si, sr, sp, sc, n, H, W, a, b, self.image_size, self.patch, out.data_ptr(), stream_ptr()),
+                "rf_siglip_preprocess")
+        return out
+
+    def preprocess_levels(self, levels: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[B, 3, H, W] (or [3, H, W]) 8-bit levels -> patch rows [B, T, K_pad]."""
+        x = levels[None] if levels.dim() == 3 else levels
+        x = x.to(self.device, BF).contiguous()                          # integers <= 256 are exact in bf16
+        B, _, H, W = x.shape
+        out = self.alloc_patches(B) if out is None else out
+        return self.preprocess(x, (3 * H * W, W, 1, H * W), 1.0 / 255.0, 0.0, out, H, W, B)
+
+    def workspace_bytes(self, nb: int) -> int:
+        return _ws_bytes(L.load().rf_siglip_vision_workspace_bytes(C.byref(self._w), nb), "rf_siglip_vision_workspace_bytes")
+
+    @torch.no_grad()
+    def encode(self, patches: torch.Tensor) -> torch.Tensor:
+        """patch rows [B, T, K_pad] -> pooler_output [B, hidden] bf16 (up to 64 images per launch sequence)."""
+        if not patches.is_cuda:
+            raise RFError("HipSiglipVisionEncoder.encode: patches are on the CPU; the HIP path has no CPU fallback")
+        B = patches.shape[0]
+        lib, w = L.load(), self._w
+        patches = patches.contiguous()
+        out = torch.empty(B, self.hidden, dtype=BF, device=self.device)
+        for b0 in range(0, B, self.MAX_BATCH):
+            nb = min(self.MAX_BATCH, B - b0)
+            ws = self._ws.get(self.workspace_bytes(nb))
+            L.check(lib.rf_siglip_vision_encode(C.byref(w), patches[b0].data_ptr(), nb, out[b0].data_ptr(), C.byref(ws), stream_ptr()),
+                    "rf_siglip_vision_encode")
+        return out
+
+
+class HipSiglipTextEncoder:
+    """SiglipTextModel of a `SiglipModel` state dict (`text_model.*`): ids [B, S] -> pooler_output [B, projection_size] bf16 =
+    head(final_layer_norm(x)[:, S - 1]).  No causal mask; S = 64 (max_length padding) for every published checkpoint."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], num_heads: int, device, eps: float = 1e-6):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RFError(f"HipSiglipTextEncoder: device {device}; the HIP path has no CPU fallback")
+        L.load()
+        sd = {(k[len("text_model."):] if k.startswith("text_model.") else k): v for k, v in state_dict.items()}
+        n_layers = _count_layers(sd, "HipSiglipTextEncoder")
+        D = sd["embeddings.token_embedding.weight"].shape[1]
+        d = siglip_head_dim("HipSiglipTextEncoder", D, num_heads)
+        self.device, self.heads, self.hidden, self.proj_dim = device, num_heads, D, sd["head.weight"].shape[0]
+        k = self._k = _Keep(device)
+        f = lambda t: t.detach().float()  # noqa: E731
+        packed = siglip_pack_layers(sd, n_layers, num_heads)
+        self._layers = _siglip_layer_structs(k, packed)
+        w = self._w = L.rf_siglip_text_weights()
+        w.layers, w.hidden, w.heads, w.head_dim, w.inter = n_layers, D, num_heads, d, packed[0]["w_fc1"].shape[0]
+        w.vocab, w.max_pos = sd["embeddings.token_embedding.weight"].shape[0], sd["embeddings.position_embedding.weight"].shape[0]
+        w.proj_dim, w.eps = self.proj_dim, eps
+        w.tok_embed, w.pos_embed = k.t(sd["embeddings.token_embedding.weight"]), k.t(sd["embeddings.position_embedding.weight"])
+        w.final_ln_scale, w.final_ln_shift = k.t(f(sd["final_layer_norm.weight"]) - 1.0), k.t(sd["final_layer_norm.bias"])
+        w.head_w, w.head_b = k.t(_kpad(sd["head.weight"])), k.t(sd["head.bias"])
+        w.layer = C.cast(self._layers, C.POINTER(L.rf_clip_layer))
+        self._mask: Dict[int, torch.Tensor] = {}
+        self._ws = _Workspace(device)
+
+    def workspace_bytes(self, nb: int, S: int) -> int:
+        return _ws_bytes(L.load().rf_siglip_text_workspace_bytes(C.byref(self._w), nb, S), "rf_siglip_text_workspace_bytes")
+
+    @torch.no_grad()
+    def encode(self, ids: torch.Tensor) -> torch.Tensor:
+        if not ids.is_cuda:
+            raise RFError("HipSiglipTextEncoder.encode: ids are on the CPU; the HIP path has no CPU fallback")
+        B, S = ids.shape
+        lib, w = L.load(), self._w
+        sp = _pad32(S)
+        w.mask, w.mask_S = None, sp
+        if sp != S:                                  # padded keys masked; never a causal mask
+            if S not in self._mask:
+                m = torch.zeros(sp, sp, device=self.device)
+                m[:, S:] = float("-inf")
+                self._mask[S] = m.contiguous()
+            w.mask = self._mask[S].data_ptr()
+        ids32 = ids.to(torch.int32).contiguous()
+        out = torch.empty(B, self.proj_dim, dtype=BF, device=self.device)
+        for b0 in range(0, B, 64):
+            nb = min(64, B - b0)
+            ws = self._ws.get(self.workspace_bytes(nb, S))
+            L.check(lib.rf_siglip_text_encode(C.byref(w), ids32[b0].data_ptr(), nb, S, out[b0].data_ptr(), C.byref(ws), stream_ptr()),
+                    "rf_siglip_text_encode")
+        return out
+
+
+def siglip_score(image_embeds: torch.Tensor, text_embed: torch.Tensor, logit_scale: float, logit_bias: float,
+                 threshold: float = 0.5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """rf_siglip_score: (sigmoid(exp(logit_scale) cos(image_embeds[b], text_embed) + logit_bias) f32 [B], labels i32 [B] = score >=
+    threshold), both on the device."""
+    img = image_embeds.to(BF).contiguous()
+    txt = text_embed.reshape(-1).to(BF).contiguous()
+    B, P = img.shape
+    if txt.numel() != P or not (img.is_cuda and txt.is_cuda):
+        raise RFError(f"siglip_score: image embeds {tuple(img.shape)} vs text embed {tuple(text_embed.shape)} (both on the device)")
+    out = torch.empty(B, dtype=torch.float32, device=img.device)
+    lab = torch.empty(B, dtype=torch.int32, device=img.device)
+    if B:
+        L.check(L.load().rf_siglip_score(img.data_ptr(), txt.data_ptr(), float(logit_scale), float(logit_bias), float(threshold), out.data_ptr(),
+                                         lab.data_ptr(), B, P, stream_ptr()), "rf_siglip_score")
+    return out, lab

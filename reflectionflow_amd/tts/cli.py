@@ -60,6 +60,12 @@ def main(mode: str, argv=None):
         from .clip_verifier import build_from_config
         v = build_from_config(config, pipe, synthetic=args.synthetic, small=args.small)
         kw = dict(score_batch=v.score_batch, score_images=v.score_images)
+    if mode == "reflection" and config.get("verifier_args", {}).get("name") == "siglip":
+        # verifier_args = {"name": "siglip", "siglip_model_path": DIR, "threshold": 0.5}: the on-device SigLIP verifier
+        # (tts/siglip_verifier.py): a calibrated probability and a real label, sorted with nvila_sort_key
+        from .siglip_verifier import build_from_config as build_siglip
+        v = build_siglip(config, pipe, synthetic=args.synthetic, small=args.small)
+        kw = dict(score_batch=v.score_batch, score_images=v.score_images)
     if mode == "reflection" and args.imgpath:
         # tts_reflectionflow.py:535-565: prompts and the round-1 pool come from the --imgpath tree (one folder per prompt with
         # metadata.jsonl + samples/), i.e. from a tts_t2i_noise_scaling output directory

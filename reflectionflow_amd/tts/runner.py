@@ -54,8 +54,8 @@ def build_pipeline(config: dict, device, synthetic: bool = False, small: bool = 
     if synthetic:
         cfg = dict(num_layers=2, num_single_layers=2, num_attention_heads=2, joint_attention_dim=256,
                    pooled_projection_dim=64) if small else None
-        # the CLIP verifier scores decoded images: a random-init VAE comes with it (the small one: 8x, channels the HIP VAE takes)
-        with_vae = config.get("verifier_args", {}).get("name") in ("clip", "pickscore")
+        # the CLIP and SigLIP verifiers score decoded images: a random-init VAE comes with it (the small one: 8x, channels the HIP VAE takes)
+        with_vae = config.get("verifier_args", {}).get("name") in ("clip", "pickscore", "siglip")
         vcfg = dict(block_out_channels=(64, 64, 128, 128), norm_num_groups=32, mid_block_add_attention=False) if small else None
         pipe = FluxPipeline.synthetic(cfg, seed=0, torch_dtype=dtype, device=device, with_vae=with_vae, vae_config=vcfg)
     else:
